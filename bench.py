@@ -1,12 +1,21 @@
 """Headline benchmark: images/sec of the ViT-B/16 int4-weight / int8-activation forward at batch 256
 per GPU (BASELINE.json configs[1]; N > 1 = configs[2], batch-sharded with an RCCL all-gather of logits).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 256] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] ...
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N ranks itself
 (torch.distributed.run as a child process, before anything touches the GPU) and exits with its code.
 Under a launcher, WORLD_SIZE must equal --gpus.
+
+A plain run sets up, warms up, times the K steps and prints the line with the headline figure and the fc1
+roofline (its events sit inside the timed region). Everything that takes work of its own runs only with --full:
+the event-timed pass over the other hot kernels (`kernels` beyond fc1), the N > 1 gather check, `cpu_baseline`
+and `parity`. --dump-outputs DIR writes what the last timed step returned (all logits, or UltraNet's flattened
+detections) to DIR/<name>.npy in float32, rank 0 only; inputs and weights are seeded, so two builds run with the
+same arguments can be compared output for output. An output over the size limit is stored as a fixed seeded
+sample of its elements.
 
 A step = one forward of the quantized ViT-B/16 over this rank's batch of synthetic 224x224 images
 already resident in HBM, plus the logits all-gather when N > 1 (distributed.ShardedInference).
@@ -17,13 +26,13 @@ epilogue). achieved = 2*M*N*K int8 ops per launch / its mean duration measured w
 around every fc1 launch inside the timed region (events on the launch stream); peak = gfx950 dense
 int8 MFMA rate; traffic = HBM bytes per launch from rocprofv3 PMC counters (profiles/fc1_traffic.json,
 written by tools/profile_fc1.sh) or null. `kernels` gives the same event timing for every hot kernel
-of the block (fused qkv+attention, proj, fc2, LayerNorm) with its algorithmic work, taken in a second,
-untimed pass of the same steps (so the timed region carries only fc1's events); `model_frac` is the
-whole forward's int8 GEMM ops / ms_per_step / peak. `parity` (N = 1, after timing, parity_report): on the
+of the block (fused qkv+attention, proj, fc2, LayerNorm) with its algorithmic work, taken with --full in a
+second, untimed pass of the same steps (so the timed region carries only fc1's events); `model_frac` is the
+whole forward's int8 GEMM ops / ms_per_step / peak. `parity` (--full, N = 1, after timing, parity_report): on the
 seed-12345 b2 images, the untied distance to the oracle split into weight-code and activation-code sources, and
 the tie-resolved check (every quantizer boundary against the oracle's, oracle/ties.py) whose `pass` is the
 tests' criterion.
-cpu_baseline: the CPU oracle's fp32 fake-quant forward (the reference's op sequence restated,
+cpu_baseline (--full): the CPU oracle's fp32 fake-quant forward (the reference's op sequence restated,
 oracle/quant_oracle.py) on a bounded sample of the same workload, rank 0 only, N = 1 only, with as
 many intra-op threads as this process may run on (affinity, capped by a cgroup CPU quota).
 
@@ -83,12 +92,35 @@ def parse(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256, help="images per GPU")
     ap.add_argument("--model", default="vit_base_patch16_224")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also time the other hot kernels, check the gather (N > 1), run the CPU baseline and parity")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
     ap.add_argument("--cpu-batch", type=int, default=8, help="CPU baseline sample (images)")
     ap.add_argument("--cpu-iters", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--lib", default="", help=argparse.SUPPRESS)  # diagnostic: A/B another build of the library
     return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 60_000_000   # all files of one --dump-outputs together stay under 64 MB
+
+
+def dump_outputs(dirpath: str, outputs: dict) -> None:
+    """--dump-outputs: each tensor as DIR/<name>.npy in float32 (float64 stays float64). One over its share of
+    DUMP_LIMIT_BYTES is stored as a fixed sample of its flattened elements (seed 0, ascending positions), the
+    same positions in every run of the same shape."""
+    import numpy as np
+    os.makedirs(dirpath, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(outputs)
+    for name, t in outputs.items():
+        t = t.detach().cpu()
+        a = (t if t.dtype == torch.float64 else t.float()).contiguous().numpy()
+        if a.nbytes > share:
+            keep = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(keep)]
+        np.save(os.path.join(dirpath, name + ".npy"), a)
 
 
 def _wreg() -> str:
@@ -381,23 +413,26 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()
+            out = step()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         _step_marker()
         events = {"fc1": vit_model.KERNEL_TIMING.pop("fc1")}
-        # the other hot kernels: the same steps again with events around each of their launches (untimed)
-        for n in names[1:]:
-            vit_model.KERNEL_TIMING[n] = []
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        for n in names[1:]:
-            events[n] = vit_model.KERNEL_TIMING.pop(n)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"logits": out})
+        if args.full:
+            # the other hot kernels: the same steps again with events around each of their launches (untimed)
+            for n in names[1:]:
+                vit_model.KERNEL_TIMING[n] = []
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            for n in names[1:]:
+                events[n] = vit_model.KERNEL_TIMING.pop(n)
         gather_ok = None
-        if world > 1:   # untimed: the gathered rows of this rank are exactly its own forward
+        if args.full and world > 1:   # untimed: the gathered rows of this rank are exactly its own forward
             from quantized_vit_amd.distributed import shard_bounds
             s, e = shard_bounds(global_batch, world, rank)
             ok = torch.tensor([1 if torch.equal(step()[s:e], model(x)) else 0], dtype=torch.int32,
@@ -421,7 +456,7 @@ def main():
     pmc = load_profile_json("pmc_mfma.json", args.model, B)
 
     kernels = {}
-    for n in names:
+    for n in events:
         ms = launch_ms[n]
         if ms is None:
             continue
@@ -482,7 +517,7 @@ def main():
     }
     if gather_ok is not None:
         result["gather_check"] = gather_ok
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         def gpu_logits(img):
             return model(img.to(dev)).cpu()
         cb, rel, floor = cpu_baseline(model, args.model, gpu_logits, img_size, args.cpu_batch, args.cpu_iters)
@@ -546,20 +581,23 @@ def ultranet_main(args, world: int, rank: int, dev, backend: str, one_device: bo
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            sharded.forward_shard(x, global_batch)
+            out = sharded.forward_shard(x, global_batch)
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
         _step_marker()
         events = {"ultra_conv0": vit_model.KERNEL_TIMING.pop("ultra_conv0")}
-        for n in names[1:]:
-            vit_model.KERNEL_TIMING[n] = []
-        for _ in range(args.steps):
-            sharded.forward_shard(x, global_batch)
-        torch.cuda.synchronize()
-        for n in names[1:]:
-            events[n] = vit_model.KERNEL_TIMING.pop(n)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {"detections": out})
+        if args.full:
+            for n in names[1:]:
+                vit_model.KERNEL_TIMING[n] = []
+            for _ in range(args.steps):
+                sharded.forward_shard(x, global_batch)
+            torch.cuda.synchronize()
+            for n in names[1:]:
+                events[n] = vit_model.KERNEL_TIMING.pop(n)
     launch_ms = {n: sum(s.elapsed_time(e) for s, e in ev) / len(ev) for n, ev in events.items() if ev}
     t = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if backend == "gloo" else dev)
     if world > 1:
@@ -600,7 +638,7 @@ def ultranet_main(args, world: int, rank: int, dev, backend: str, one_device: bo
                        "frac_hbm_peak": img_bytes * value / world / 1e9 / HBM_PEAK_GBS},
         "kernels": kernels,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import ultranet_oracle as U
         sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
         img = synthetic_images_u8(args.cpu_batch, size, seed=12345)
@@ -649,10 +687,12 @@ def dryrun_main(args, world: int, rank: int) -> None:
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        sharded.forward_shard(x, global_batch)
+        out = sharded.forward_shard(x, global_batch)
     if world > 1:
         dist.barrier()
     t = torch.tensor([time.perf_counter() - t0], dtype=torch.float64)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": out})
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())

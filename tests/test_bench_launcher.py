@@ -34,6 +34,40 @@ def test_bench_gpus_flag_launches_n_ranks(n):
     assert j["steps"] == 3 and j["value"] > 0 and j["scaling"] == "weak"
 
 
+def test_dump_outputs_is_repeatable_and_plain_line_is_lean(tmp_path):
+    """--dump-outputs writes the last timed step's outputs as float32 .npy, identical from run to run; a plain
+    run's line carries the headline fields and nothing that --full alone measures."""
+    import numpy as np
+    got = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "4", "--dump-outputs", str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert os.listdir(tmp_path / d) == ["logits.npy"]
+        got.append(np.load(tmp_path / d / "logits.npy"))
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert got[0].dtype == np.float32 and got[0].shape == (4, 10)
+    assert np.array_equal(got[0], got[1])
+    assert j["steps"] == 2 and j["ms_per_step"] > 0 and j["unit"] == "img/s" and j["higher_is_better"] is True
+    assert abs(j["value"] - 4 / (j["ms_per_step"] * 1e-3)) <= 1e-6 * j["value"]
+    assert not {"cpu_baseline", "parity", "gather_check"} & set(j)
+
+
+def test_dump_outputs_samples_a_large_output(tmp_path, monkeypatch):
+    """An output over the size limit is stored as the same seeded sample of its elements every time."""
+    import numpy as np
+    import torch
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4000)
+    t = torch.arange(5000, dtype=torch.float32).reshape(50, 100)
+    bench.dump_outputs(str(tmp_path / "a"), {"big": t, "small": t[:2].double()})
+    bench.dump_outputs(str(tmp_path / "b"), {"big": t.clone(), "small": t[:2].double()})
+    big, small = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "a" / "small.npy")
+    assert big.dtype == np.float32 and big.shape == (500,) and (np.diff(big) > 0).all()   # 2000 B share, no repeats
+    assert small.dtype == np.float64 and np.array_equal(small, t[:2].numpy())
+    assert np.array_equal(big, np.load(tmp_path / "b" / "big.npy"))
+    assert big.nbytes + small.nbytes <= 4000
+
+
 def test_bench_world_size_mismatch_is_an_error():
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0"],
              extra_env={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})

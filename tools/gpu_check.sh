@@ -25,10 +25,10 @@ if [[ $STEPS == *tests* ]]; then
   if [[ $rc -ge 2 ]]; then echo "pytest crashed/timed out (rc=$rc): stopping"; exit $rc; fi
 fi
 if [[ $STEPS == *bench* ]]; then
-  run bench 360 python bench.py ${BENCH_ARGS:-} || exit $?
+  run bench 360 python bench.py --full ${BENCH_ARGS:-} || exit $?
 fi
 if [[ $STEPS == *prof* ]]; then
-  run rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline || exit $?
+  run rocprof 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline || exit $?
   find "$OUT/prof" -name "*kernel_stats*" -exec cp {} "$OUT/" \; 2>/dev/null
 fi
 echo ALL DONE

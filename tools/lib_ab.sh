@@ -18,7 +18,7 @@ for r in $(seq 1 "$ROUNDS"); do
   if [ "${MODEL:-1}" = 1 ]; then
     for lib in "$@"; do
       tag=$(basename "$lib" .so)
-      timeout -k 10 240 python bench.py --no-cpu-baseline --steps 20 --warmup 3 --lib "$lib" > "$OUT/b_${tag}_$r.log" 2>&1 \
+      timeout -k 10 240 python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 --lib "$lib" > "$OUT/b_${tag}_$r.log" 2>&1 \
         || { echo "bench $tag failed"; tail -5 "$OUT/b_${tag}_$r.log"; exit 1; }
       echo "== model $tag round $r: $(grep '^{' "$OUT/b_${tag}_$r.log" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["value"]), "img/s", round(d["ms_per_step"], 3), "ms", {k: round(v["launch_us"], 1) for k, v in d["kernels"].items()})')"
     done

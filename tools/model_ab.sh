@@ -13,14 +13,14 @@ use() { if [ "$1" = b ]; then cp "$ALT" "$LIB"; else cp "$O/lib_a.so.keep" "$LIB
 rc=0
 for tag in a b a b; do
   use $tag
-  timeout -k 10 200 python bench.py --no-cpu-baseline --steps 20 --warmup 3 > "$O/b_$tag.log" 2>&1 || { tail -5 "$O/b_$tag.log"; rc=1; break; }
+  timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 > "$O/b_$tag.log" 2>&1 || { tail -5 "$O/b_$tag.log"; rc=1; break; }
   echo "$tag $(grep '^{' "$O/b_$tag.log" | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(d["value"], d["ms_per_step"])')"
 done
 if [ $rc -eq 0 ]; then
   for tag in a b; do
     use $tag
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/s_$tag" -o run -- \
-        python bench.py --steps 5 --warmup 2 --no-cpu-baseline > "$O/s_$tag.log" 2>&1 || { tail -5 "$O/s_$tag.log"; rc=1; break; }
+        python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$O/s_$tag.log" 2>&1 || { tail -5 "$O/s_$tag.log"; rc=1; break; }
     f=$(find "$O/s_$tag" -name "*kernel_stats.csv" | head -1)
     echo "== $tag"; python tools/kstats.py "$f" 8
   done

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   d="$OUT/pmc_${c,,}"
   timeout -k 10 400 rocprofv3 --pmc $c --kernel-trace --output-format csv -d "$d" -o run -- \
-      python bench.py --steps 2 --warmup 1 --no-cpu-baseline > "$d.log" 2>&1
+      python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > "$d.log" 2>&1
   rc=$?
   echo "pmc $c rc=$rc"
   if [ $rc -ne 0 ]; then tail -5 "$d.log"; exit $rc; fi

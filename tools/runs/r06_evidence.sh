@@ -8,14 +8,14 @@ mkdir -p $O
 export TMPDIR=/tmp
 OUT=$O bash tools/gpu_round.sh \
   "600|tests|python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread" \
-  "300|bench|python bench.py" \
-  "400|rocprof|QVIT_STEP_MARKERS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp -o run -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline" \
+  "300|bench|python bench.py --full" \
+  "400|rocprof|QVIT_STEP_MARKERS=1 rocprofv3 --kernel-trace --stats --output-format csv -d $O/rp -o run -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline" \
   "600|fc1_traffic|OUT=$O/fc1 ROUND=r06 bash tools/profile_fc1.sh" \
   "900|pmc|OUT=$O/pmc ROUND=r06 bash tools/profile_model_pmc.sh" \
-  "300|bench2|python bench.py" \
+  "300|bench2|python bench.py --full" \
   "120|smoke|python -c 'import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")'" \
-  "400|bench_vitl|python bench.py --model vit_large_patch16_384 --batch 128" \
-  "300|bench_ultra|python bench.py --model ultranet" || exit $?
+  "400|bench_vitl|python bench.py --full --model vit_large_patch16_384 --batch 128" \
+  "300|bench_ultra|python bench.py --full --model ultranet" || exit $?
 cp profiles/fc1_traffic_r06.json profiles/fc1_traffic.json $O/ 2>/dev/null
 cp $O/pmc/pmc_mfma.json $O/pmc_mfma_r06.json 2>/dev/null
 f=$(find $O/rp -name "*kernel_trace.csv" | head -1)

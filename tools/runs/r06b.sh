@@ -11,7 +11,7 @@ for r in 1 2; do
     echo "== gemm $w $r"; grep -v '^{\|amdgpu.ids' $O/g_${w}_$r.log
   done
   for w in w4r w8r; do
-    QVIT_GEMM_WREG=$w timeout -k 10 200 python bench.py --no-cpu-baseline --steps 20 --warmup 3 > $O/b_${w}_$r.log 2>&1 || { tail -5 $O/b_${w}_$r.log; exit 1; }
+    QVIT_GEMM_WREG=$w timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 20 --warmup 3 > $O/b_${w}_$r.log 2>&1 || { tail -5 $O/b_${w}_$r.log; exit 1; }
     echo "== model $w $r: $(grep '^{' $O/b_${w}_$r.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print(round(d["value"]), "img/s", round(d["ms_per_step"], 3), "ms", {k: round(v["launch_us"], 1) for k, v in d["kernels"].items()})')"
   done
 done
