@@ -11,6 +11,10 @@
  *                             also 4-bit quantization/quant_ultra.py:59-73 (activation_quantize_fn).
  *   qvit_fake_quant_f32       the same quantizers emitting the reference's fp32 fake-quant values
  *                             (used when a layer's level count does not fit int8, e.g. num_bits > 8).
+ *   qvit_quant_backward       quant_layers.py:71-125 (SymQuantizerNonLinear.backward), :163-205
+ *                             (SymQuantizerLinear.backward) and :248-290 (DGEQuantizer.backward): grad_x and the
+ *                             three quantizer-scalar gradients in one streaming pass with a deterministic
+ *                             two-stage reduction (the reference: ~30 elementwise launches and three host syncs).
  *   qvit_pack_weight          quant_layers.py:332-354 (QuantizeMixin.quantize_weight) + the GEMM operand
  *                             layout: codes packed int4 (8 per u32) or int8, rows padded/permuted.
  *   qvit_im2col_quant_i8      quant_layers.py:575-587 (QuantizeConv2d.forward): the conv input patches
@@ -126,6 +130,32 @@ int qvit_quantize_act_i8(const float* x, int64_t rows, int64_t cols, int64_t ldx
 int qvit_fake_quant_f32(const float* x, int64_t n, int qtype, const float* d_quant,
                         const float* q_m, const float* t_quant, int levels, float* y,
                         hipStream_t stream);
+
+/*
+ * Backward of the fake quantizers over n contiguous floats (q_s = 0): SymQuantizerLinear.backward
+ * (quant_layers.py:163-205), SymQuantizerNonLinear.backward (:71-125) and, with dge_k > 0, DGEQuantizer.backward
+ * (:248-290; linear forward only, k = 5 * 4 / num_bits as :236 derives it).
+ *   grad_x        : grad_out, zeroed where x >= clip_hi or x <= clip_lo (:77-79, :169-171); with dge_k > 0 then
+ *                   scaled by (1/k) |x - d/2|^(1/k - 1) and clamped to +-3 (:259-265). May alias grad_out.
+ *   grad_scalars  : float[3] = sum(grad_out * term) for d_quant, q_m, t_quant (:95, :99, :105, :183, :187);
+ *                   the t_quant sum is 0 for the linear quantizer. With a = |x|, p = a or exp(t log a), q = p / d:
+ *                     d    : sgn(x) (rne(q) - q); sgn(x) (L - range_pow / d) where a >= q_m; 0 where a <= 0
+ *                     q_m  : sgn(x) (linear) or sgn(x) t exp((t - 1) log(|q_m| + 1e-6)), only where a > q_m
+ *                     t    : sgn(x) p log a; sgn(x) range_pow log(|q_m| + 1e-6) where a >= q_m; 0 where a <= 0
+ *                   rne(q) is the code qvit_fake_quant_f32 / qvit_quantize_act_i8 produce for the same element.
+ *                   Masks select (a masked element never contributes a NaN); a NaN in grad_out or in a parameter
+ *                   reaches the sums, which is what the reference's NanInGradientError checks (:108-123, :190-204).
+ *   workspace     : qvit_quant_backward_workspace_bytes(n) bytes, 8-byte aligned: one partial per workgroup,
+ *                   folded in a fixed order by a second launch (no float atomics: a call is bitwise reproducible).
+ * x, grad_out and grad_x must be 16-byte aligned. qtype is QVIT_QT_LINEAR or QVIT_QT_NONLINEAR (t_quant required).
+ * n == 0 writes three zeros. qvit_quant_backward_workspace_bytes returns QVIT_EINVAL for n < 0.
+ */
+int64_t qvit_quant_backward_workspace_bytes(int64_t n);
+int qvit_quant_backward(const float* x, const float* grad_out, int64_t n, int qtype,
+                        const float* d_quant, const float* q_m, const float* t_quant,
+                        float clip_lo, float clip_hi, float dge_k,
+                        float* grad_x, float* grad_scalars /* [3] */,
+                        void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 /*
  * y = GELU(x) elementwise over n contiguous floats: nn.GELU() (QViT_with_GETA/vit_model.py:173,242), bit-identical

@@ -58,6 +58,7 @@ _f32 = ctypes.c_float
 _SIGNATURES = {
     "qvit_quantize_act_i8": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i64, _c_p],
     "qvit_fake_quant_f32": [_c_p, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
+    "qvit_quant_backward": [_c_p, _c_p, _i64, _i32, _c_p, _c_p, _c_p, _f32, _f32, _f32, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_gelu_f32": [_c_p, _i64, _c_p, _c_p],
     "qvit_pack_weight": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i64, _c_p, _c_p],
     "qvit_pad_bias": [_c_p, _i64, _c_p, _i64, _c_p],
@@ -105,6 +106,7 @@ _SIGNATURES = {
 }
 # name -> argtypes of the entry points returning int64_t
 INT64_FUNCS = {
+    "qvit_quant_backward_workspace_bytes": [_i64],
 }
 STRING_FUNCS = {"qvit_strerror": [_i32], "qvit_version": []}
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(INT64_FUNCS) + list(STRING_FUNCS))
@@ -212,6 +214,33 @@ def fake_quant_f32(x: torch.Tensor, qtype: int, d: Optional[torch.Tensor], qm: O
     _check(load().qvit_fake_quant_f32(_ptr(xc), xc.numel(), qtype, _ptr(d), _ptr(qm), _ptr(t), levels, _ptr(y),
                                       _stream(x.device)), "qvit_fake_quant_f32")
     return y
+
+
+def quant_backward(x: torch.Tensor, grad_out: torch.Tensor, qtype: int, d: torch.Tensor, qm: torch.Tensor,
+                   t: Optional[torch.Tensor], clip_lo: float, clip_hi: float, dge_k: float = 0.0,
+                   grad_x: Optional[torch.Tensor] = None):
+    """Backward of the fake quantizer over x (qvit_quant_backward). Returns (grad_x, scalars): grad_x shaped as x
+    (written into `grad_x` when given; it may be grad_out itself) and the float32 [3] sums for d_quant, q_m and
+    t_quant, on the device (no host sync)."""
+    _require_gpu(x, "input")
+    _require_gpu(grad_out, "grad_out")
+    xc = x.detach().contiguous().float()
+    gc = grad_out.detach().contiguous().float()
+    if xc.numel() != gc.numel():
+        raise QvitError(f"quant_backward: grad_out has {gc.numel()} elements for an input of {xc.numel()}")
+    if grad_x is None:
+        grad_x = torch.empty_like(xc)
+    assert grad_x.is_cuda and grad_x.dtype == torch.float32 and grad_x.is_contiguous() and \
+        grad_x.numel() == xc.numel()
+    n = xc.numel()
+    lib = load()
+    nbytes = int(lib.qvit_quant_backward_workspace_bytes(n))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=xc.device)
+    scalars = torch.empty(3, dtype=torch.float32, device=xc.device)
+    _check(lib.qvit_quant_backward(_ptr(xc), _ptr(gc), n, qtype, _ptr(d), _ptr(qm), _ptr(t), float(clip_lo),
+                                   float(clip_hi), float(dge_k), _ptr(grad_x), _ptr(scalars), _ptr(ws), nbytes,
+                                   _stream(xc.device)), "qvit_quant_backward")
+    return grad_x, scalars
 
 
 def gelu_f32(x: torch.Tensor) -> torch.Tensor:

@@ -19,7 +19,12 @@ Layers whose levels do not fit int8 (e.g. the 16/32-bit initial states, weight-o
 the reference's fake-quant values (HIP kernel qvit_fake_quant_f32) through the library fp32
 GEMM instead. CPU tensors are rejected: the product has no CPU fallback.
 
-Inference only: the HIP path does not record autograd history (training / GETA is out of scope).
+Autograd: a layer called with gradients enabled, and an input or a parameter that requires grad, records
+one autograd node around the very same forward (bit-identical output). Its backward runs the two GEMM
+gradients on torch's fp32 GEMM and the reference's quantizer backwards (quant_layers.py:71-125, 163-205) as
+one fused HIP pass each (qvit_quant_backward): grad_x plus the gradients of d_quant, q_m and t_quant through
+a deterministic reduction. SymQuantizerLinear / SymQuantizerNonLinear / DGEQuantizer expose the same pass at
+the function level. Under torch.no_grad() nothing of this runs. The GETA optimizer is out of scope.
 """
 from __future__ import annotations
 
@@ -42,7 +47,7 @@ logger = logging.getLogger(__name__)
 
 
 class NanInGradientError(Exception):
-    """quant_layers.py:10-13 (raised by the reference's backward; kept for API parity)."""
+    """quant_layers.py:10-13: raised by a quantizer's backward when its gradient holds a NaN."""
 
     def __init__(self, message):
         self.message = message
@@ -92,6 +97,11 @@ def _warn_no_grad() -> None:
                       "(inference only); run under torch.no_grad() to silence this warning.")
 
 
+def _autograd_live(module: nn.Module, x: torch.Tensor) -> bool:
+    """Whether a call of `module` on `x` has to record autograd history."""
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
 def _as_param_ptr(p: Optional[torch.Tensor], device: torch.device) -> Optional[torch.Tensor]:
     if p is None:
         return None
@@ -112,6 +122,111 @@ def saturation_level(qtype: int, d: float, q_m: float, t: float = 1.0) -> float:
             p = np.exp(f(t) * np.log(np.abs(f(q_m)) + f(1e-6)), dtype=np.float32)
         q = f(p) / f(d)
     return float(np.rint(q)) if np.isfinite(q) else float("inf")
+
+
+# ---- quantizer autograd functions (quant_layers.py:33-290) -----------------------------------------
+def _clip_pair(clip_val) -> Tuple[float, float]:
+    if isinstance(clip_val, torch.Tensor):
+        clip_val = clip_val.detach().cpu().tolist()
+    lo, hi = clip_val
+    return float(lo), float(hi)
+
+
+def _check_q_s(q_s) -> None:
+    """q_s is 0 everywhere in the reference's callers (quant_layers.py:335,362); a host value is checked, a
+    device tensor is taken on trust (reading it would sync)."""
+    if q_s is None or (isinstance(q_s, torch.Tensor) and q_s.is_cuda):
+        return
+    if float(q_s) != 0.0:
+        raise NotImplementedError("the HIP quantizers implement q_s = 0 only")
+
+
+def _nan_message(what: str, names, tensors, host) -> str:
+    vals = ", ".join(f"{n}: {float(v.reshape(-1)[0]):.5f}" for n, v in zip(names, tensors) if v is not None)
+    return (f"Error: NaN appears in gradient ({what})!\n{vals}, q_s: 0\n"
+            f"grad_d: {host[0]:.5f}\ngrad_qm: {host[1]:.5f}\ngrad_t: {host[2]:.5f}")
+
+
+def _quantizer_forward(ctx, input_, d_quant, q_m, t_quant, clip_val, q_s, qtype: int, dge_k: float):
+    _check_q_s(q_s)
+    dev = input_.device
+    d, qm, t = (_as_param_ptr(p, dev) for p in (d_quant, q_m, t_quant))
+    ctx.save_for_backward(input_, d, qm, t)
+    ctx.qtype, ctx.dge_k, ctx.clip = qtype, dge_k, _clip_pair(clip_val)
+    ctx.like = [None if p is None else (p.shape, p.device, p.dtype) for p in (d_quant, q_m, t_quant)]
+    return _lib.fake_quant_f32(input_.detach(), qtype, d, qm, t).to(input_.dtype)
+
+
+def _quantizer_backward(ctx, grad_output):
+    """(grad_x, [grad_d, grad_qm, grad_t] shaped as the parameters, device scalars, saved tensors)."""
+    input_, d, qm, t = ctx.saved_tensors
+    gx, scal = _lib.quant_backward(input_, grad_output, ctx.qtype, d, qm, t, ctx.clip[0], ctx.clip[1], ctx.dge_k)
+    grads = [None if like is None else scal[i:i + 1].reshape(like[0]).to(device=like[1], dtype=like[2])
+             for i, like in enumerate(ctx.like)]
+    return gx.to(input_.dtype), grads, scal, (d, qm, t)
+
+
+class SymQuantizerLinear(torch.autograd.Function):
+    """quant_layers.py:128-205 on the device: qvit_fake_quant_f32 forward, qvit_quant_backward backward."""
+
+    @staticmethod
+    def forward(ctx, input, d_quant, q_m, clip_val, q_s):
+        return _quantizer_forward(ctx, input, d_quant, q_m, None, clip_val, q_s, _lib.QT_LINEAR, 0.0)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gx, grads, scal, params = _quantizer_backward(ctx, grad_output)
+        host = scal.cpu().tolist()   # the one host sync (the reference syncs on the same check, :190-204)
+        if math.isnan(host[0]):
+            raise NanInGradientError(_nan_message("grad_d", ("d", "q_m"), params, host))
+        return gx, grads[0], grads[1], None, None
+
+
+class SymQuantizerNonLinear(torch.autograd.Function):
+    """quant_layers.py:33-125 on the device."""
+
+    @staticmethod
+    def forward(ctx, input, d_quant, q_m, t_quant, clip_val, q_s):
+        return _quantizer_forward(ctx, input, d_quant, q_m, t_quant, clip_val, q_s, _lib.QT_NONLINEAR, 0.0)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gx, grads, scal, params = _quantizer_backward(ctx, grad_output)
+        host = scal.cpu().tolist()   # :108-123
+        if math.isnan(host[2]):
+            raise NanInGradientError(_nan_message("grad_t", ("d", "q_m", "t"), params, host))
+        return gx, grads[0], grads[1], grads[2], None, None
+
+
+class DGEQuantizer(torch.autograd.Function):
+    """quant_layers.py:208-290 on the device: the linear quantizer's forward; the backward scales grad_x by
+    (1/k) |x - d/2|^(1/k - 1), k = 5 * 4 / num_bits (:236), clamped to +-3."""
+
+    @staticmethod
+    def forward(ctx, input, d_quant, q_m, clip_val, q_s, num_bits):
+        k = 5.0 * (4.0 / float(num_bits))
+        if not k > 0.0:
+            raise ValueError(f"DGEQuantizer: num_bits = {float(num_bits)} gives k = {k}")
+        return _quantizer_forward(ctx, input, d_quant, q_m, None, clip_val, q_s, _lib.QT_LINEAR, k)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gx, grads, scal, params = _quantizer_backward(ctx, grad_output)
+        host = torch.cat([scal, torch.isnan(gx).any().reshape(1).float()]).cpu().tolist()   # :281
+        if host[3]:
+            raise NanInGradientError(_nan_message(f"grad_x, k: {ctx.dge_k:.4f}", ("d", "q_m"), params, host))
+        return gx, grads[0], grads[1], None, None, None
+
+
+def _get_quantizer(qtype: QuantizationType):
+    """quant_layers.py:292-300."""
+    if qtype == QuantizationType.SYMMETRIC_LINEAR:
+        return SymQuantizerLinear
+    if qtype == QuantizationType.SYMMETRIC_NONLINEAR:
+        return SymQuantizerNonLinear
+    if qtype == QuantizationType.DGE:
+        return DGEQuantizer
+    raise NotImplementedError
 
 
 def _round_up(v: int, m: int) -> int:
@@ -206,7 +321,27 @@ class QuantizeMixin:
         self._weight_codes: Optional[Tuple[tuple, torch.Tensor]] = None
 
     # -- reference API: fake-quant fp32 tensors (quant_layers.py:332-381) -------------------
+    def _quantize_fn(self, x: torch.Tensor, which: str, clip_val) -> torch.Tensor:
+        """The quantizer as an autograd function (quant_layers.py:336-354, 363-381)."""
+        quantizer = _get_quantizer(self.quant_type)
+        d, qm = getattr(self, f"d_quant_{which}"), getattr(self, f"q_m_{which}")
+        if self.quant_type == QuantizationType.SYMMETRIC_LINEAR:
+            return quantizer.apply(x, d, qm, clip_val, 0.0)
+        return quantizer.apply(x, d, qm, getattr(self, f"t_quant_{which}"), clip_val, 0.0)
+
+    def _records_grad(self, x: torch.Tensor) -> bool:
+        """Autograd-live and a quantizer type the modules can differentiate (DGE through the modules has no
+        backward, here as in the reference, :346-354: it is exposed as DGEQuantizer only)."""
+        if not _autograd_live(self, x):
+            return False
+        if self.quant_type == QuantizationType.DGE:
+            _warn_no_grad()
+            return False
+        return True
+
     def quantize_weight(self, weight: torch.Tensor) -> torch.Tensor:
+        if self._records_grad(weight):
+            return self._quantize_fn(weight, "wt", self.weight_clip_val)
         dev = weight.device
         return _lib.fake_quant_f32(weight.detach(), _qtype_code(self.quant_type),
                                    _as_param_ptr(self.d_quant_wt, dev), _as_param_ptr(self.q_m_wt, dev),
@@ -215,6 +350,8 @@ class QuantizeMixin:
     def quantize_act(self, activation: torch.Tensor) -> torch.Tensor:
         if self.quant_mode != QuantizationMode.WEIGHT_AND_ACTIVATION:
             return activation
+        if self._records_grad(activation):
+            return self._quantize_fn(activation, "act", self.act_clip_val)
         dev = activation.device
         return _lib.fake_quant_f32(activation.detach(), _qtype_code(self.quant_type),
                                    _as_param_ptr(self.d_quant_act, dev), _as_param_ptr(self.q_m_act, dev),
@@ -458,9 +595,74 @@ class QuantizeMixin:
         if not x.is_cuda:
             raise _lib.QvitError(f"{type(self).__name__}: input on {x.device}; the HIP path needs a ROCm "
                                  "device tensor (no CPU fallback)")
-        if torch.is_grad_enabled() and (x.requires_grad or any(
-                p is not None and p.requires_grad for p in self._quant_param_tensors())):
-            _warn_no_grad()
+
+    # -- autograd (quant_layers.py:71-125, 163-205 behind F.linear / F.conv2d's own backward) ------
+    def _forward_autograd(self, input_: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
+        g = lambda n: getattr(self, n, None)
+        return _QuantLayerFunction.apply(self, plan, input_, self.weight, self.bias, g("d_quant_wt"), g("q_m_wt"),
+                                         g("t_quant_wt"), g("d_quant_act"), g("q_m_act"), g("t_quant_act"))
+
+    def _gemm_grads(self, plan: QuantPlan, xshape: tuple, x_q: Optional[torch.Tensor],
+                    w_q: Optional[torch.Tensor], G: torch.Tensor):
+        """Gradients of the contraction on torch's fp32 GEMM / convolution: (w.r.t. the quantized input, when
+        w_q is given; w.r.t. the quantized weight, when x_q is given), contiguous fp32."""
+        raise NotImplementedError
+
+    def _backward_plan(self, plan: QuantPlan, x: torch.Tensor, weight: torch.Tensor, G: torch.Tensor,
+                       needs: tuple) -> tuple:
+        """Gradients of _forward_plan's output for (input, weight, bias, d_quant_wt, q_m_wt, t_quant_wt,
+        d_quant_act, q_m_act, t_quant_act); None where `needs` is false (that work is skipped)."""
+        wa = self.quant_mode == QuantizationMode.WEIGHT_AND_ACTIVATION
+        need_x, need_w, need_b = needs[0], needs[1], needs[2]
+        need_wq = need_w or any(needs[3:6])          # the weight quantizer's backward runs
+        need_aq = wa and (need_x or any(needs[6:9]))   # the activation quantizer's backward runs
+        need_xq = need_aq or need_x
+        G = G.detach().float().contiguous()
+        xf = x.detach().float().contiguous()
+        grad_b = None
+        if need_b:
+            grad_b = (G.sum((0, 2, 3)) if isinstance(self, nn.Conv2d) else G.reshape(-1, plan.n).sum(0)) \
+                .to(self.bias.dtype)
+        # the operands the forward contracted: quantize_weight(W), and d_act * codes (fake_quant_f32 and the int8
+        # paths share quant_code) or the input itself in weight-only mode
+        w_q = self.w_fakequant(plan).view_as(weight) if need_xq else None
+        x_q = None
+        if need_wq:
+            x_q = _lib.fake_quant_f32(xf, plan.qtype, plan.d_act, plan.qm_act, plan.t_act) if wa else xf
+        grad_xq, grad_wq = self._gemm_grads(plan, tuple(xf.shape), x_q, w_q, G)
+        quantizers = []   # (which, grad through the quantizer, device scalars)
+        grad_x = grad_xq
+        if need_aq:
+            grad_x, scal = _lib.quant_backward(xf, grad_xq, plan.qtype, plan.d_act, plan.qm_act, plan.t_act,
+                                               self.act_clip_val[0], self.act_clip_val[1], grad_x=grad_xq)
+            quantizers.append(("act", scal))
+        grad_w = None
+        if need_wq:
+            wf = weight.detach().float().contiguous()
+            grad_w, scal = _lib.quant_backward(wf, grad_wq, plan.qtype, plan.d_wt, plan.qm_wt, plan.t_wt,
+                                               self.weight_clip_val[0], self.weight_clip_val[1], grad_x=grad_wq)
+            quantizers.append(("wt", scal))
+        scalars = {}
+        if quantizers:
+            # one readback for both quantizers' NaN checks (:108-123 grad_t, :190-204 grad_d)
+            host = torch.cat([sc for _, sc in quantizers]).cpu().tolist()
+            chk = 2 if plan.qtype == _lib.QT_NONLINEAR else 0
+            for i, (which, sc) in enumerate(quantizers):
+                scalars[which] = sc
+                h = host[3 * i:3 * i + 3]
+                if math.isnan(h[chk]):
+                    params = [getattr(self, f"{n}_{which}", None) for n in ("d_quant", "q_m", "t_quant")]
+                    raise NanInGradientError(_nan_message(
+                        f"{type(self).__name__} {which} quantizer, {'grad_t' if chk else 'grad_d'}",
+                        ("d", "q_m", "t"), params, h))
+        out = [grad_x.view_as(x).to(x.dtype) if need_x else None,
+               grad_w.view_as(weight).to(weight.dtype) if need_w else None,
+               grad_b]
+        for j, which in ((3, "wt"), (6, "act")):
+            for i, name in enumerate(("d_quant", "q_m", "t_quant")):
+                p = getattr(self, f"{name}_{which}", None)
+                out.append(scalars[which][i:i + 1].reshape(p.shape).to(p.dtype) if needs[j + i] else None)
+        return tuple(out)
 
     def _act_codes(self, x2d: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
         M = x2d.shape[0]
@@ -472,6 +674,8 @@ class QuantizeMixin:
                    out: Optional[torch.Tensor] = None, next_layer: Optional["QuantizeMixin"] = None) -> torch.Tensor:
         """Runs the contraction on activation codes (int8 [M, kpad]) with the given epilogue.
         EPI_I8 / EPI_I8_GELU quantize the result with `next_layer`'s activation quantizer."""
+        if torch.is_grad_enabled() and _autograd_live(self, codes):
+            _warn_no_grad()   # a direct low-level call: only the modules' forward() records autograd history
         M = codes.shape[0]
         dev = codes.device
         oq = dict(out_qtype=0)
@@ -568,6 +772,23 @@ def epilogue_table(nplan: QuantPlan, epilogue: int) -> Optional[torch.Tensor]:
     return nplan.extra[key]
 
 
+class _QuantLayerFunction(torch.autograd.Function):
+    """One autograd node around a layer's forward: the value is _forward_plan's (the code that runs under
+    no_grad, on whichever path the plan selects), the backward is QuantizeMixin._backward_plan."""
+
+    @staticmethod
+    def forward(ctx, module, plan, input_, weight, bias, d_wt, qm_wt, t_wt, d_act, qm_act, t_act):
+        ctx.module, ctx.plan = module, plan
+        ctx.save_for_backward(input_, weight)
+        return module._forward_plan(input_, plan)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        input_, weight = ctx.saved_tensors
+        grads = ctx.module._backward_plan(ctx.plan, input_, weight, grad_output, tuple(ctx.needs_input_grad[2:]))
+        return (None, None) + grads
+
+
 def initialize_quant_layer(layer, num_bits: int = 16,
                            quant_type: QuantizationType = QuantizationType.SYMMETRIC_LINEAR,
                            quant_mode: QuantizationMode = QuantizationMode.WEIGHT_ONLY) -> None:
@@ -618,6 +839,17 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
     def forward(self, input_: torch.Tensor) -> torch.Tensor:
         self._check_input(input_)
         plan = self.quant_plan()
+        if self._records_grad(input_):
+            return self._forward_autograd(input_, plan)
+        return self._forward_plan(input_, plan)
+
+    def _gemm_grads(self, plan, xshape, x_q, w_q, G):
+        G2 = G.reshape(-1, plan.n)
+        grad_xq = torch.mm(G2, w_q.reshape(plan.n, plan.k)) if w_q is not None else None
+        grad_wq = torch.mm(G2.t(), x_q.reshape(-1, plan.k)) if x_q is not None else None
+        return grad_xq, grad_wq
+
+    def _forward_plan(self, input_: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
         if plan.int_path:
             x2 = input_.detach().reshape(-1, plan.k)
             if x2.dtype != torch.float32 or x2.stride(-1) != 1:
@@ -691,6 +923,30 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
     def forward(self, input_: torch.Tensor) -> torch.Tensor:
         self._check_input(input_)
         plan = self.quant_plan()
+        if self._records_grad(input_):
+            return self._forward_autograd(input_, plan)
+        return self._forward_plan(input_, plan)
+
+    def _gemm_grads(self, plan, xshape, x_q, w_q, G):
+        need_xq, need_wq = w_q is not None, x_q is not None
+        if isinstance(self.padding, str) or self.padding_mode != "zeros":
+            # paddings torch.nn.grad does not take: differentiate the library convolution itself
+            with torch.enable_grad():
+                xin = (x_q if need_wq else torch.zeros(xshape, device=G.device)).detach().requires_grad_(need_xq)
+                win = (w_q if need_xq else torch.zeros_like(self.weight, dtype=torch.float32)).detach() \
+                    .requires_grad_(need_wq)
+                y = self._conv_forward(xin, win, None)
+                got = list(torch.autograd.grad(y, [t for t in (xin, win) if t.requires_grad], G))
+            grad_xq = got.pop(0).contiguous() if need_xq else None
+            grad_wq = got.pop(0).contiguous() if need_wq else None
+            return grad_xq, grad_wq
+        args = (self.stride, self.padding, self.dilation, self.groups)
+        grad_xq = torch.nn.grad.conv2d_input(xshape, w_q, G, *args).contiguous() if need_xq else None
+        grad_wq = torch.nn.grad.conv2d_weight(x_q, tuple(self.weight.shape), G, *args).contiguous() \
+            if need_wq else None
+        return grad_xq, grad_wq
+
+    def _forward_plan(self, input_: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
         if plan.int_path and self._int_conv_ok():
             out, (B, OH, OW) = self.conv_codes_gemm(input_)
             n = plan.n

@@ -12,7 +12,10 @@ place by the GEMM epilogues):
     (qvit_qkv_attention, N <= 208; longer sequences: qkv GEMM to fp16 hi/lo head planes -> streaming
     attention) -> proj GEMM (+= residual) -> LayerNorm+act-quant -> fc1 GEMM with GELU and fc2's
     act-quant fused (int8 codes out) -> fc2 GEMM (+= residual)
-Otherwise each module runs on its own (still the HIP kernels for every quantized layer).
+Otherwise each module runs on its own (still the HIP kernels for every quantized layer). That is also the
+route when the call records autograd history (gradients enabled and the input or a parameter requires grad):
+the fused pipeline, the HIP attention and the in-place token buffer have no backward, so every module runs on
+its own and the quantized layers differentiate through quant_layers' autograd node.
 """
 from __future__ import annotations
 
@@ -29,7 +32,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import quant_layers as _ql
-from .quant_layers import QuantizationMode, QuantizeConv2d, QuantizeLinear, epilogue_table, trace_codes
+from .quant_layers import (QuantizationMode, QuantizeConv2d, QuantizeLinear, _autograd_live, epilogue_table,
+                           trace_codes)
 
 # The residual GEMMs (proj, fc2) run the following LayerNorm + quantizer behind their tiles (qvit_gemm_resid_ln)
 # instead of as a separate launch when QVIT_FUSE_LN=1 (or FUSE_RESID_LN = True). Off by default: the fused
@@ -105,7 +109,7 @@ class PatchEmbed(nn.Module):
         if not torch.jit.is_tracing():
             assert H == self.img_size[0] and W == self.img_size[1], \
                 f"Input image size ({H}*{W}) doesn't match model ({self.img_size[0]}*{self.img_size[1]})."
-        if _conv_int_path(self.proj, x):
+        if _conv_int_path(self.proj, x) and not _autograd_live(self.proj, x):
             # im2col+quant -> GEMM rows are already (b, patch) x embed: no flatten/transpose copy
             out, (B, OH, OW) = self.proj.conv_codes_gemm(x)
             n = self.proj.quant_plan().n
@@ -150,7 +154,7 @@ class ViTAttention(nn.Module):
 
     def core(self, qkv: torch.Tensor, B: int, N: int) -> torch.Tensor:
         """softmax(q k^T * scale) v on the qkv projection (vit_model.py:133-149), fp32."""
-        if self.hip_ok(qkv.reshape(B * N, -1)):
+        if not (torch.is_grad_enabled() and qkv.requires_grad) and self.hip_ok(qkv.reshape(B * N, -1)):
             q2 = qkv.reshape(B * N, -1)
             out = torch.empty((B * N, self.num_heads * 64), dtype=torch.float32, device=qkv.device)
             amax = float(q2.abs().max()) if q2.numel() else 0.0   # unfused path: no plan bound, one sync
@@ -241,6 +245,7 @@ class Block(nn.Module):
     def fused_ok(self, x: torch.Tensor) -> bool:
         a, m = self.attn, self.mlp
         return (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3
+                and not _autograd_live(self, x)
                 and isinstance(self.norm1, nn.LayerNorm) and isinstance(self.norm2, nn.LayerNorm)
                 and self.norm1.elementwise_affine and self.norm2.elementwise_affine
                 and isinstance(m.act, nn.GELU) and m.act.approximate == "none"
@@ -451,7 +456,9 @@ class VisionTransformer(nn.Module):
 
     def forward_features(self, x):
         x = self.patch_embed(x)
-        if x.is_cuda and _inactive(self.pos_drop):
+        live = torch.is_grad_enabled() and (x.requires_grad or any(
+            p is not None and p.requires_grad for p in (self.pos_embed, self.cls_token, self.dist_token)))
+        if x.is_cuda and _inactive(self.pos_drop) and not live:
             # cat((cls[, dist], x)) + pos_embed in one pass: the token rows are written straight into the
             # residual buffer (the same fp32 additions as the reference's cat-then-add)
             B, T, C = x.shape
