@@ -37,6 +37,8 @@
  *   qvit_attention            vit_model.py:133-149 (Attention.forward between qkv and proj):
  *                             softmax(q k^T * scale) v per (image, head), fp32 out or fused with the
  *                             proj layer's quantize_act (quant_layers.py:497) -> int8 codes.
+ *   qvit_attention_backward   the gradient autograd takes through vit_model.py:133-149 (dq, dk, dv from dO),
+ *                             softmax recomputed on chip, nothing N x N in memory.
  *
  * Conventions
  *   - Plain pointers and sizes only. All pointers are device pointers (hipMalloc'd / torch CUDA
@@ -466,6 +468,31 @@ int qvit_attention(const float* qkv, int64_t B, int64_t N, int64_t H, int64_t he
                    float scale, float in_scale, int out_mode, void* out, int64_t ldo,
                    int out_qtype, const float* out_d, const float* out_qm, const float* out_t,
                    int out_levels, hipStream_t stream);
+
+/*
+ * Backward of qvit_attention with QVIT_ATT_F32 (the gradient torch autograd takes through vit_model.py:133-149):
+ * with S = scale q k^T, P = softmax(S), O = P v and D_i = sum_c dO_ic O_ic,
+ *   dv = P^T dO,  dS = P o (dO v^T - D),  dq = scale dS k,  dk = scale dS^T q.
+ * S and P are recomputed per 32-row block on chip; nothing N x N reaches global memory.
+ *   qkv      : fp32 [B N][ldq], the forward's input (q, k, v sections of H * 64 columns); ldq >= 3 H 64
+ *   out      : fp32 [B N][ldo], the forward's output O (required); ldo >= H 64
+ *   grad_out : fp32 [B N][ldgo], dO; ldgo >= H 64
+ *   grad_qkv : fp32 [B N][ldg], written in the layout of qkv (columns [0, 3 H 64) only); ldg >= 3 H 64
+ *   in_scale : the forward's power of two (|qkv in_scale| <= 16384)
+ *   g_scale  : a power of two with |grad_out g_scale| <= 16384, as close to it as the caller can make it (gradients
+ *              of 1e-8 would flush in the fp16 operand split); undone exactly, so grad(a dO) = a grad(dO) bit for
+ *              bit for a power of two a when g_scale follows max |dO|
+ *   workspace: qvit_attention_backward_workspace_bytes(B, N, H) bytes (O(B H N): one log-sum-exp and one D per
+ *              query, one bound per head), 16-byte aligned, caller-owned, no state carried between calls.
+ * head_dim must be 64; every pointer 16-byte aligned and every leading dimension a multiple of 4. Three launches
+ * (row sums, query owner -> dq, key owner -> dk, dv), no float atomics: a call is bitwise reproducible.
+ * qvit_attention_backward_workspace_bytes returns QVIT_EINVAL for N <= 0, H <= 0 or B < 0.
+ */
+int64_t qvit_attention_backward_workspace_bytes(int64_t B, int64_t N, int64_t H);
+int qvit_attention_backward(const float* qkv, const float* out, const float* grad_out, int64_t B, int64_t N,
+                            int64_t H, int64_t head_dim, int64_t ldq, int64_t ldo, int64_t ldgo, float scale,
+                            float in_scale, float g_scale, float* grad_qkv, int64_t ldg, void* workspace,
+                            int64_t workspace_bytes, hipStream_t stream);
 
 /*
  * The qkv projection feeding qvit_attention_split (fused block path; replaces the fp32 qkv of

@@ -103,10 +103,13 @@ _SIGNATURES = {
                            _i32, _c_p, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
     "qvit_attention_split": [_c_p, _c_p, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _c_p, _i64, _i32, _c_p, _c_p,
                              _c_p, _i32, _c_p, _c_p],
+    "qvit_attention_backward": [_c_p, _c_p, _c_p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _c_p,
+                                _i64, _c_p, _i64, _c_p],
 }
 # name -> argtypes of the entry points returning int64_t
 INT64_FUNCS = {
     "qvit_quant_backward_workspace_bytes": [_i64],
+    "qvit_attention_backward_workspace_bytes": [_i64, _i64, _i64],
 }
 STRING_FUNCS = {"qvit_strerror": [_i32], "qvit_version": []}
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(INT64_FUNCS) + list(STRING_FUNCS))
@@ -541,6 +544,35 @@ def attention(qkv: torch.Tensor, B: int, N: int, H: int, head_dim: int, scale: f
                                  out.stride(0), out_qtype, _ptr(out_d), _ptr(out_qm), _ptr(out_t), out_levels,
                                  _stream(qkv.device)), "qvit_attention")
     return out
+
+
+def attention_backward_workspace_bytes(B: int, N: int, H: int) -> int:
+    return int(load().qvit_attention_backward_workspace_bytes(B, N, H))
+
+
+def attention_backward(qkv: torch.Tensor, out: torch.Tensor, grad_out: torch.Tensor, B: int, N: int, H: int,
+                       head_dim: int, scale: float, in_scale: float = 1.0, g_scale: float = 1.0,
+                       grad_qkv: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Gradient of attention() with respect to qkv (qvit_attention_backward): qkv [B*N, >= 3*H*hd], out and
+    grad_out [B*N, >= H*hd], all fp32 with unit column stride. Returns grad_qkv shaped like qkv's [B*N, 3*H*hd]
+    columns (written into `grad_qkv` when given; columns past 3*H*hd are left alone)."""
+    for t, name in ((qkv, "qkv"), (out, "out"), (grad_out, "grad_out")):
+        _require_gpu(t, name)
+        assert t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.shape[0] == B * N, name
+    if grad_qkv is None:
+        grad_qkv = torch.empty((B * N, 3 * H * head_dim), dtype=torch.float32, device=qkv.device)
+    _require_gpu(grad_qkv, "grad_qkv")
+    assert grad_qkv.dtype == torch.float32 and grad_qkv.dim() == 2 and grad_qkv.stride(1) == 1
+    lib = load()
+    nbytes = int(lib.qvit_attention_backward_workspace_bytes(B, N, H))
+    if nbytes < 0:
+        _check(nbytes, "qvit_attention_backward_workspace_bytes")
+    ws = torch.empty(max(nbytes, 16) // 4, dtype=torch.float32, device=qkv.device)
+    _check(lib.qvit_attention_backward(_ptr(qkv), _ptr(out), _ptr(grad_out), B, N, H, head_dim, qkv.stride(0),
+                                       out.stride(0), grad_out.stride(0), scale, in_scale, g_scale, _ptr(grad_qkv),
+                                       grad_qkv.stride(0), _ptr(ws), nbytes, _stream(qkv.device)),
+           "qvit_attention_backward")
+    return grad_qkv
 
 
 def gemm_qkv_split(A: torch.Tensor, M: int, K: int, packed: torch.Tensor, wfmt: int, N: int, npad: int,

@@ -14,8 +14,9 @@ place by the GEMM epilogues):
     act-quant fused (int8 codes out) -> fc2 GEMM (+= residual)
 Otherwise each module runs on its own (still the HIP kernels for every quantized layer). That is also the
 route when the call records autograd history (gradients enabled and the input or a parameter requires grad):
-the fused pipeline, the HIP attention and the in-place token buffer have no backward, so every module runs on
-its own and the quantized layers differentiate through quant_layers' autograd node.
+the fused pipeline and the in-place token buffer have no backward, so every module runs on its own: the
+quantized layers differentiate through quant_layers' autograd node and the attention core through _AttentionCore
+(qvit_attention forward, qvit_attention_backward).
 """
 from __future__ import annotations
 
@@ -120,6 +121,58 @@ class PatchEmbed(nn.Module):
         return x
 
 
+def _pow2_scale(amax: float) -> float:
+    """Power of two s with amax * s <= 16384 (the fp16 hi/lo split's range); 1 unless amax exceeds it."""
+    return 1.0 if amax <= 16384.0 else 2.0 ** -math.ceil(math.log2(amax / 16384.0))
+
+
+def _pow2_grad_scale(gmax: float) -> float:
+    """qvit_attention_backward's g_scale: the largest power of two s with gmax * s <= 16384 (gradients are
+    scaled up as well as down: 1e-8 would flush in the fp16 split), kept inside fp32's exponent range."""
+    if not math.isfinite(gmax) or gmax == 0.0:
+        return 1.0
+    return 2.0 ** max(-100, min(100, 14 - math.ceil(math.log2(gmax))))
+
+
+def _attention_core_forward(q2: torch.Tensor, B: int, N: int, H: int, scale: float):
+    """qvit_attention (fp32 out) on the [B*N, 3*H*64] qkv projection. Returns (out, in_scale)."""
+    out = torch.empty((B * N, H * 64), dtype=torch.float32, device=q2.device)
+    amax = float(q2.abs().max()) if q2.numel() else 0.0   # unfused path: no plan bound, one sync
+    in_scale = _pow2_scale(amax)
+    _lib.attention(q2, B, N, H, 64, scale, out, _lib.ATT_F32, in_scale)
+    return out, in_scale
+
+
+class _AttentionCore(torch.autograd.Function):
+    """ViTAttention.core on the HIP kernels under autograd: the forward is the no_grad call (same bits), the
+    backward one qvit_attention_backward. Saves qkv and the output only: nothing of size N x N."""
+
+    @staticmethod
+    def forward(ctx, q2, B, N, H, scale):
+        q2 = q2.detach()
+        if q2.stride(1) != 1 or q2.stride(0) % 4 or q2.data_ptr() % 16:
+            q2 = q2.contiguous()
+        out, in_scale = _attention_core_forward(q2, B, N, H, scale)
+        ctx.save_for_backward(q2, out)
+        ctx.meta = (B, N, H, scale, in_scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        q2, out = ctx.saved_tensors
+        B, N, H, scale, in_scale = ctx.meta
+        g = grad_out.detach()
+        if g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1 or g.stride(0) % 4 or g.data_ptr() % 16:
+            g = g.float().contiguous()
+        gmax = float(g.abs().max()) if g.numel() else 0.0      # one sync, as in_scale in the forward
+        g_scale = _pow2_grad_scale(gmax)
+        dqkv = torch.empty((B * N, q2.shape[1]), dtype=torch.float32, device=q2.device)
+        if q2.shape[1] > 3 * H * 64:
+            dqkv[:, 3 * H * 64:] = 0
+        _lib.attention_backward(q2, out, g, B, N, H, 64, scale, in_scale, g_scale, dqkv)
+        return dqkv, None, None, None, None
+
+
 class ViTAttention(nn.Module):
     """vit_model.py:106-153."""
 
@@ -154,12 +207,12 @@ class ViTAttention(nn.Module):
 
     def core(self, qkv: torch.Tensor, B: int, N: int) -> torch.Tensor:
         """softmax(q k^T * scale) v on the qkv projection (vit_model.py:133-149), fp32."""
-        if not (torch.is_grad_enabled() and qkv.requires_grad) and self.hip_ok(qkv.reshape(B * N, -1)):
-            q2 = qkv.reshape(B * N, -1)
-            out = torch.empty((B * N, self.num_heads * 64), dtype=torch.float32, device=qkv.device)
-            amax = float(q2.abs().max()) if q2.numel() else 0.0   # unfused path: no plan bound, one sync
-            scale = 1.0 if amax <= 16384.0 else 2.0 ** -math.ceil(math.log2(amax / 16384.0))
-            return self.core_hip(q2, B, N, out, _lib.ATT_F32, scale).reshape(B, N, -1)
+        if self.hip_ok(qkv.reshape(B * N, -1)):
+            if torch.is_grad_enabled() and qkv.requires_grad:   # same kernel, with qvit_attention_backward behind it
+                return _AttentionCore.apply(qkv.reshape(B * N, -1), B, N, self.num_heads,
+                                            self.scale).reshape(B, N, -1)
+            return _attention_core_forward(qkv.reshape(B * N, -1), B, N, self.num_heads, self.scale)[0].reshape(
+                B, N, -1)
         qkv = qkv.reshape(B, N, 3, self.num_heads, -1).permute(2, 0, 3, 1, 4)
         q, k, v = qkv[0], qkv[1], qkv[2]
         attn = (q @ k.transpose(-2, -1)) * self.scale
