@@ -225,7 +225,9 @@ int qvit_im2col_quant_i8(const float* x, int64_t B, int64_t C, int64_t H, int64_
 /*
  * LayerNorm (biased variance, eps) followed by the next layer's activation quantizer.
  *   x : fp32 [rows][ldx] (D = cols), gamma/beta fp32 [cols] (may be NULL -> 1 / 0)
- *   codes : int8 [rows][ldc], columns [cols, kpad) zero.
+ *   codes : int8 [rows][ldc], columns [cols, kpad) zero; 4-byte aligned, ldc % 4 == 0. Columns [kpad, ldc) and x
+ *            columns [cols, ldx) are never touched. Any ldx and any alignment of x / gamma / beta is accepted (rows
+ *            with cols % 4, ldx % 4 or a base off 16 bytes take a scalar kernel, as do cols > 2048).
  *   code_table : nullable, 16-B aligned; a qvit_epi_table_build table (QVIT_EPI_I8 semantics) of the
  *            same quantizer, used only if valid and <= 2046 buckets (results never depend on it).
  */

@@ -585,11 +585,7 @@ int qvit_layernorm_quant_i8(const float* x, int64_t rows, int64_t cols, int64_t 
 #define QVIT_LN_REG(NV)                                                                                   \
   hipLaunchKernelGGL(layernorm_quant_reg_kernel<NV>, grid, dim3(kThreads), 0, stream, x, rows, cols, ldx, \
                      gamma, beta, eps, qtype, d_quant, q_m, t_quant, levels, codes, ldc, kpad)
-  if (reg && nv <= 1) QVIT_LN_REG(1);
-  else if (reg && nv <= 2) QVIT_LN_REG(2);
-  else if (reg && nv <= 3) QVIT_LN_REG(3);
-  else if (reg && nv <= 4) QVIT_LN_REG(4);
-  else if (reg && nv <= 8) QVIT_LN_REG(8);
+  if (reg && nv <= 8) QVIT_LN_REG(8);  // cols 1025 .. 2048 (nv <= 4 took the persistent kernel above)
   else
     hipLaunchKernelGGL(layernorm_quant_kernel, dim3(grid_for(rows * 64, kThreads)), dim3(kThreads), 0, stream, x,
                        rows, cols, ldx, gamma, beta, eps, qtype, d_quant, q_m, t_quant, levels, codes, ldc, kpad);
