@@ -28,6 +28,9 @@
  *   qvit_gemm_wonly           quant_layers.py:495-499 in the default WEIGHT_ONLY mode (quant_model.py:23): fp32
  *                             activations x int4/int8 weight codes on bf16 MFMA (x split into three exact
  *                             bf16 terms), d_wt * acc + bias — F.linear(x, quantize_weight(W), b).
+ *   qvit_gemm_wgrad           the backward of quant_layers.py:499's F.linear w.r.t. the quantized weight on the
+ *                             integer path: fp32 grad_out^T x int8 activation codes on bf16 MFMA (the same exact
+ *                             three-term split); the input's gradient is qvit_gemm_wonly on transposed codes.
  *   qvit_conv_wonly           quant_layers.py:575-587 (QuantizeConv2d.forward, WEIGHT_ONLY) and quant_ultra.py:85-89
  *                             (Conv2d_Q.forward): the same contraction as an implicit GEMM over the NCHW input
  *                             (patches gathered in the kernel), NCHW fp32 out — F.conv2d(x, quantize_weight(W), b).
@@ -303,6 +306,37 @@ int qvit_gemm_a32(const int8_t* A, int64_t M, int64_t K, const void* Wp, int wfm
 int qvit_gemm_wonly(const float* X, int64_t M, int64_t K, int64_t ldx, const void* Wp, int wfmt,
                     int64_t N, int64_t npad, const float* d_wt, const float* bias, float* Y, int64_t ldy,
                     float* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/*
+ * The backward GEMMs of QuantizeLinear (what autograd runs behind quant_layers.py:499's F.linear, with G the
+ * gradient of the layer's output):
+ *   dgrad  grad_xq[m, k] = sum_n G[m, n] (d_wt k_w[n, k])  is qvit_gemm_wonly itself: X = G (zero columns up to
+ *          the image's reduction padding), Wp = the qvit_pack_weight image of the TRANSPOSED codes (rows = the
+ *          layer's in-features, reduction = its out-features), bias = NULL. No new entry point.
+ *   wgrad  dW[n, k] = d_act * sum_m G[m, n] A[m, k]  (qvit_gemm_wgrad), A the int8 activation codes the forward
+ *          contracted (qvit_quantize_act_i8: x_q = d_act A), dW in the layout of nn.Linear.weight.grad.
+ *   G      : fp32 [M][ldg], N valid columns; ldg % 4 == 0, 16-byte aligned.
+ *   A      : int8 [M][lda], K valid columns, |code| <= 127; lda % 16 == 0, 16-byte aligned. Columns [K, lda) are
+ *            padding: whatever they hold never reaches dW.
+ *   d_act  : device float[1].
+ *   dW     : fp32 [N][ldw], ldw >= K (any 4-byte aligned pointer and any ldw); columns [K, ldw) are not written.
+ *   workspace : qvit_gemm_wgrad_workspace_bytes(M, N, K) bytes, 16-byte aligned, contents irrelevant. The M range
+ *            is split over s = max(1, min(16, ceil(M / 32), ceil(512 / tiles))) workgroups per output tile (tiles =
+ *            ceil(N / 128) ceil(K / 128)); their fp32 partials (s tiles of 128 x 128 each) are summed in ascending
+ *            split order by a second launch: no atomics, the same call gives the same bits. The query returns
+ *            s * 128 ceil(N / 128) * 128 ceil(K / 128) * 4: non-decreasing in M, at most 16 times the padded
+ *            output and at most (tiles + 511) * 64 KiB (Mlp.fc1 of ViT-B: 4 N K 4 bytes).
+ * Any M >= 0, N >= 1, K >= 1 (M <= 2^30, N, K <= 2^24, tiles <= 2^24; else QVIT_EINVAL, also from the query);
+ * misaligned G / A / workspace or ldg / lda: QVIT_EALIGN (callers pad a copy). Rows m >= M contribute zero. M == 0
+ * writes zeros.
+ * fp32-GEMM accuracy, as qvit_gemm_wonly: G is split into three bf16 terms whose sum is G exactly, every product
+ * with a code (7 significant bits) is exact in fp32, accumulation is fp32 on v_mfma_f32_16x16x32_bf16, one multiply
+ * by d_act ends it. A NaN / inf in G[m][n] leaves row n of dW NaN and no other row.
+ */
+int64_t qvit_gemm_wgrad_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int qvit_gemm_wgrad(const float* G, int64_t M, int64_t N, int64_t ldg, const int8_t* A, int64_t K, int64_t lda,
+                    const float* d_act, float* dW, int64_t ldw, void* workspace, int64_t workspace_bytes,
+                    hipStream_t stream);
 
 /*
  * Weight-only convolution (QuantizeConv2d.forward, quant_layers.py:575-587, quant_mode WEIGHT_ONLY; UltraNet's

@@ -76,6 +76,7 @@ _SIGNATURES = {
     "qvit_gemm_a32": [_c_p, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i32, _c_p, _c_p,
                       _c_p, _i32, _c_p, _c_p],
     "qvit_gemm_wonly": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i64, _c_p, _i64, _c_p],
+    "qvit_gemm_wgrad": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i64, _c_p, _i64, _c_p],
     "qvit_conv_wonly": [_c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_p, _i32,
                         _i64, _i64, _i64, _c_p, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_conv_wonly_bn_act": [_c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_p,
@@ -110,6 +111,7 @@ _SIGNATURES = {
 INT64_FUNCS = {
     "qvit_quant_backward_workspace_bytes": [_i64],
     "qvit_attention_backward_workspace_bytes": [_i64, _i64, _i64],
+    "qvit_gemm_wgrad_workspace_bytes": [_i64, _i64, _i64],
 }
 STRING_FUNCS = {"qvit_strerror": [_i32], "qvit_version": []}
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(INT64_FUNCS) + list(STRING_FUNCS))
@@ -435,6 +437,52 @@ def gemm_wonly(X: torch.Tensor, M: int, K: int, packed: torch.Tensor, wfmt: int,
                                   _ptr(bias_pad), _ptr(Y), Y.stride(0), _ptr(ws), 0 if ws is None else ws.numel() * 4,
                                   _stream(X.device)), "qvit_gemm_wonly")
     return Y
+
+
+def gemm_wgrad_splits(M: int, N: int, K: int) -> int:
+    """Workgroups per output tile over which qvit_gemm_wgrad splits the M range (from its workspace query)."""
+    r = lambda v: (v + 127) // 128 * 128
+    nbytes = int(load().qvit_gemm_wgrad_workspace_bytes(M, N, K))
+    if nbytes < 0:
+        raise QvitError(f"qvit_gemm_wgrad_workspace_bytes({M}, {N}, {K}) failed (status {nbytes})")
+    return nbytes // (r(N) * r(K) * 4)
+
+
+def gemm_wgrad(G: torch.Tensor, codes: torch.Tensor, K: int, d_act: torch.Tensor,
+               out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dW[N, K] = d_act * G^T @ codes[:, :K] (qvit_gemm_wgrad): G fp32 [M, N], codes int8 [M, >= K] (the forward's
+    activation codes). An operand off the kernel's alignment (row stride of G not a multiple of 4, of the codes not
+    a multiple of 16, base not 16-byte aligned) is copied into a padded buffer first. `out`: fp32 [N, >= K] rows
+    (columns past K stay untouched); `workspace`: float32, at least the query's bytes (contents irrelevant)."""
+    _require_gpu(G, "grad_out")
+    _require_gpu(codes, "codes")
+    assert G.dim() == 2 and codes.dim() == 2 and codes.dtype == torch.int8 and codes.shape[0] == G.shape[0]
+    assert codes.shape[1] >= K >= 1
+    M, N = G.shape
+    if G.dtype != torch.float32 or G.stride(1) != 1 or G.stride(0) % 4 or G.stride(0) < N or G.data_ptr() % 16:
+        gp = torch.zeros((M, (N + 3) // 4 * 4), dtype=torch.float32, device=G.device)
+        gp[:, :N] = G
+        G = gp
+    if codes.stride(1) != 1 or codes.stride(0) % 16 or codes.stride(0) < K or codes.data_ptr() % 16:
+        cp = torch.zeros((M, (K + 15) // 16 * 16), dtype=torch.int8, device=codes.device)
+        cp[:, :K] = codes[:, :K]
+        codes = cp
+    if out is None:
+        out = torch.empty((N, K), dtype=torch.float32, device=G.device)
+    assert out.dtype == torch.float32 and out.shape[0] == N and out.shape[1] >= K and out.stride(1) == 1
+    if M == 0:   # (an empty tensor has no device pointer to hand over)
+        out[:, :K] = 0
+        return out
+    lib = load()
+    nbytes = int(lib.qvit_gemm_wgrad_workspace_bytes(M, N, K))
+    if nbytes < 0:
+        _check(nbytes, "qvit_gemm_wgrad_workspace_bytes")
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=G.device)
+    _check(lib.qvit_gemm_wgrad(_ptr(G), M, N, G.stride(0), _ptr(codes), K, codes.stride(0), _ptr(d_act), _ptr(out),
+                               out.stride(0), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                               _stream(G.device)), "qvit_gemm_wgrad")
+    return out
 
 
 def conv_wonly(x: torch.Tensor, kernel_size, stride, padding, dilation, packed: torch.Tensor, wfmt: int, N: int,

@@ -21,7 +21,9 @@ GEMM instead. CPU tensors are rejected: the product has no CPU fallback.
 
 Autograd: a layer called with gradients enabled, and an input or a parameter that requires grad, records
 one autograd node around the very same forward (bit-identical output). Its backward runs the two GEMM
-gradients on torch's fp32 GEMM and the reference's quantizer backwards (quant_layers.py:71-125, 163-205) as
+gradients (QuantizeLinear: on the integer codes, qvit_gemm_wonly on the transposed weight codes and
+qvit_gemm_wgrad on the activation codes, see BACKWARD_GEMM; otherwise torch's fp32 GEMM / convolution) and the
+reference's quantizer backwards (quant_layers.py:71-125, 163-205) as
 one fused HIP pass each (qvit_quant_backward): grad_x plus the gradients of d_quant, q_m and t_quant through
 a deterministic reduction. SymQuantizerLinear / SymQuantizerNonLinear / DGEQuantizer expose the same pass at
 the function level. Under torch.no_grad() nothing of this runs. The GETA optimizer is out of scope.
@@ -243,6 +245,23 @@ if GEMM_WREG not in ("w4", "w4r", "w8r"):
     raise ValueError(f"QVIT_GEMM_WREG={GEMM_WREG!r}: expected w4, w4r or w8r")
 GEMM_W4R = GEMM_WREG != "w4"   # a register image is in use
 
+# The backward GEMMs of QuantizeLinear (behind F.linear's backward): "hip" runs both on the project's kernels,
+# dgrad (grad_out @ quantize_weight(W)) as qvit_gemm_wonly on the transposed weight codes wherever the plan holds
+# packed codes, wgrad (grad_out^T @ quantize_act(x)) as qvit_gemm_wgrad on the int8 activation codes of the
+# integer path; "torch" keeps both on torch.mm (fp32 library GEMMs); "dgrad" / "wgrad" select one op.
+# QVIT_BWD_GEMM sets it (the measurement behind the default: DESIGN.md section 13).
+BACKWARD_GEMM = os.environ.get("QVIT_BWD_GEMM", "hip")
+_BACKWARD_GEMM_OPS = {"hip": ("dgrad", "wgrad"), "torch": (), "dgrad": ("dgrad",), "wgrad": ("wgrad",)}
+if BACKWARD_GEMM not in _BACKWARD_GEMM_OPS:
+    raise ValueError(f"QVIT_BWD_GEMM={BACKWARD_GEMM!r}: expected hip, torch, dgrad or wgrad")
+
+
+def _backward_gemm_ops() -> tuple:
+    try:
+        return _BACKWARD_GEMM_OPS[BACKWARD_GEMM]
+    except KeyError:
+        raise ValueError(f"BACKWARD_GEMM = {BACKWARD_GEMM!r}: expected hip, torch, dgrad or wgrad") from None
+
 
 @dataclass
 class QuantPlan:
@@ -289,6 +308,15 @@ class QuantPlan:
         if self.packed is None:
             self.packed = self.extra["repack"]()
         return self.packed
+
+    def packed_t(self) -> Tuple[torch.Tensor, int, int]:
+        """(image, npad, kpad) of the TRANSPOSED weight codes in the plan's wfmt (rows = in-features padded to
+        TILE_N, reduction = out-features padded to TILE_K): the operand of the input gradient on qvit_gemm_wonly.
+        Packed on the first backward and kept with the plan (whose key follows every parameter update)."""
+        if "packed_t" not in self.extra:
+            npad_t, kpad_t = _round_up(self.k, _lib.TILE_N), _round_up(self.n, _lib.TILE_K)
+            self.extra["packed_t"] = (self.extra["pack_t"](npad_t, kpad_t), npad_t, kpad_t)
+        return self.extra["packed_t"]
 
 
 class QuantizeMixin:
@@ -498,6 +526,7 @@ class QuantizeMixin:
                 packed = _lib.pack_weight(w32, qt_pack, d_pack, qm_pack, t_pack, wfmt, npad, kpad, overflow)
                 if int(overflow.item()) == 0:
                     plan.packed, plan.wfmt, plan.int_path = packed, wfmt, True
+                    plan.extra["pack_t"] = self._packer_t(w2, codes, (qt_pack, d_pack, qm_pack, t_pack), wfmt)
                     if wfmt == _lib.W4:   # how gemm_weights() gets the packed codes back after releasing them
                         plan.extra["repack"] = self._repacker(w2, codes, (qt_pack, d_pack, qm_pack, t_pack),
                                                               wfmt, npad, kpad)
@@ -515,12 +544,14 @@ class QuantizeMixin:
                     if int(overflow.item()) == 0:
                         plan.packed, plan.wfmt = packed, wfmt
                         plan.extra["wonly"] = True
+                        plan.extra["pack_t"] = self._packer_t(w2, codes, (qt_pack, d_pack, qm_pack, t_pack), wfmt)
                         break
             else:
                 wc = codes.to(device=dev, dtype=torch.float32) if codes is not None else \
                     (_lib.fake_quant_f32(w32, qt, d_wt, qm_wt, t_wt) / d_wt).round()
                 plan.packed, plan.wfmt = _lib.pack_weight_wide(wc, npad, kpad)
                 plan.extra["wonly"] = True
+                plan.extra["pack_t"] = self._packer_t(w2, codes, (qt, d_wt, qm_wt, t_wt), 0)
         if plan.int_path or plan.extra.get("wonly"):
             bias = self.bias.detach() if self.bias is not None else None
             plan.bias_pad = _lib.pad_bias(bias, n, npad, dev)
@@ -546,6 +577,25 @@ class QuantizeMixin:
             overflow = torch.zeros(1, dtype=torch.int32, device=w2.device)
             return _lib.pack_weight(src, *qargs, wfmt, npad, kpad, overflow)
         return repack
+
+    @staticmethod
+    def _packer_t(w2: torch.Tensor, codes: Optional[torch.Tensor], qargs: tuple, wfmt: int):
+        """A closure that packs the transposed weight codes (QuantPlan.packed_t). The quantizers are elementwise, so
+        packing the transposed fp32 weight (or the transposed bound codes) gives exactly the forward's codes;
+        wfmt 0: wide codes as base-256 digits (pack_weight_wide picks W16 / W24 from the same largest code)."""
+        def pack(npad_t: int, kpad_t: int) -> torch.Tensor:
+            if codes is not None:
+                src = codes.to(device=w2.device, dtype=torch.float32)
+            else:
+                src = w2.float()
+            if wfmt == 0:
+                if codes is None:
+                    qt, d, qm, t = qargs
+                    src = (_lib.fake_quant_f32(src.contiguous(), qt, d, qm, t) / d).round()
+                return _lib.pack_weight_wide(src.t().contiguous(), npad_t, kpad_t)[0]
+            overflow = torch.zeros(1, dtype=torch.int32, device=w2.device)
+            return _lib.pack_weight(src.t().contiguous(), *qargs, wfmt, npad_t, kpad_t, overflow)
+        return pack
 
     def _fake_quant_weight(self, plan: QuantPlan) -> torch.Tensor:
         """quantize_weight(W) on the device; with codes bound by load_weight_codes, d_w * k of exactly those
@@ -608,6 +658,15 @@ class QuantizeMixin:
         w_q is given; w.r.t. the quantized weight, when x_q is given), contiguous fp32."""
         raise NotImplementedError
 
+    def _backward_gemm_routes(self, plan: QuantPlan, need_xq: bool, need_wq: bool) -> Tuple[bool, bool]:
+        """(dgrad, wgrad) on the HIP kernels (QuantizeLinear only; every other layer keeps the library)."""
+        return False, False
+
+    def _gemm_grads_hip(self, plan: QuantPlan, xf: torch.Tensor, x_q: Optional[torch.Tensor],
+                        w_q: Optional[torch.Tensor], G: torch.Tensor, hip_x: bool, hip_w: bool):
+        """_gemm_grads with the ops flagged by _backward_gemm_routes on the HIP kernels."""
+        raise NotImplementedError
+
     def _backward_plan(self, plan: QuantPlan, x: torch.Tensor, weight: torch.Tensor, G: torch.Tensor,
                        needs: tuple) -> tuple:
         """Gradients of _forward_plan's output for (input, weight, bias, d_quant_wt, q_m_wt, t_quant_wt,
@@ -625,11 +684,16 @@ class QuantizeMixin:
                 .to(self.bias.dtype)
         # the operands the forward contracted: quantize_weight(W), and d_act * codes (fake_quant_f32 and the int8
         # paths share quant_code) or the input itself in weight-only mode
-        w_q = self.w_fakequant(plan).view_as(weight) if need_xq else None
+        # (an op on its HIP route reads the integer codes instead: BACKWARD_GEMM)
+        hip_x, hip_w = self._backward_gemm_routes(plan, need_xq, need_wq)
+        w_q = self.w_fakequant(plan).view_as(weight) if need_xq and not hip_x else None
         x_q = None
-        if need_wq:
+        if need_wq and not hip_w:
             x_q = _lib.fake_quant_f32(xf, plan.qtype, plan.d_act, plan.qm_act, plan.t_act) if wa else xf
-        grad_xq, grad_wq = self._gemm_grads(plan, tuple(xf.shape), x_q, w_q, G)
+        if hip_x or hip_w:
+            grad_xq, grad_wq = self._gemm_grads_hip(plan, xf, x_q, w_q, G, hip_x, hip_w)
+        else:
+            grad_xq, grad_wq = self._gemm_grads(plan, tuple(xf.shape), x_q, w_q, G)
         quantizers = []   # (which, grad through the quantizer, device scalars)
         grad_x = grad_xq
         if need_aq:
@@ -847,6 +911,34 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
         G2 = G.reshape(-1, plan.n)
         grad_xq = torch.mm(G2, w_q.reshape(plan.n, plan.k)) if w_q is not None else None
         grad_wq = torch.mm(G2.t(), x_q.reshape(-1, plan.k)) if x_q is not None else None
+        return grad_xq, grad_wq
+
+    def _backward_gemm_routes(self, plan, need_xq, need_wq):
+        ops = _backward_gemm_ops()
+        has_codes = plan.int_path or bool(plan.extra.get("wonly"))
+        return (need_xq and "dgrad" in ops and has_codes and "pack_t" in plan.extra,
+                need_wq and "wgrad" in ops and plan.int_path)
+
+    def _gemm_grads_hip(self, plan, xf, x_q, w_q, G, hip_x, hip_w):
+        G2 = G.reshape(-1, plan.n)
+        M = G2.shape[0]
+        grad_xq, grad_wq = self._gemm_grads(plan, tuple(xf.shape), None if hip_w else x_q, None if hip_x else w_q, G)
+        if hip_x:
+            # G @ (d_wt k_w): qvit_gemm_wonly on the transposed codes (rows = in-features, reduction = out-features)
+            packed_t, npad_t, kpad_t = plan.packed_t()
+            Gp = G2
+            if G2.shape[1] != kpad_t or G2.stride(0) % 4 or G2.data_ptr() % 16:
+                Gp = torch.zeros((M, kpad_t), dtype=torch.float32, device=G2.device)
+                Gp[:, :plan.n] = G2
+            ldy = _round_up(plan.k, 4)
+            y = torch.empty((M, ldy), dtype=torch.float32, device=G2.device)
+            if M:
+                _lib.gemm_wonly(Gp, M, kpad_t, packed_t, plan.wfmt, plan.k, npad_t, plan.d_wt, None, y)
+            grad_xq = y if ldy == plan.k else y[:, :plan.k].contiguous()
+        if hip_w:
+            # G^T @ (d_act codes): the int8 codes the forward contracted (the same quant_code)
+            x2 = xf.reshape(-1, plan.k)
+            grad_wq = _lib.gemm_wgrad(G2, self._act_codes(x2, plan), plan.k, plan.d_act)
         return grad_xq, grad_wq
 
     def _forward_plan(self, input_: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
