@@ -170,6 +170,51 @@ int qvit_quant_backward(const float* x, const float* grad_out, int64_t n, int qt
 int qvit_gelu_f32(const float* x, int64_t n, float* y, hipStream_t stream);
 
 /*
+ * Train-time fusion of a QuantizeLinear's pre-op with its activation quantizer (train_fuse.hip): the backward of
+ * qvit_layernorm_quant_i8, and GELU + quantizer forward and backward. No fp32 tensor of the pre-op's output exists.
+ *
+ * qvit_layernorm_quant_backward: backward of codes = quantize(LayerNorm(x)) given grad_y, the gradient with respect
+ * to the quantizer's output (what the input-gradient GEMM returns).
+ *   x        : fp32 [rows][ldx], the LayerNorm input; gamma, beta: fp32 [cols] (both required); eps as the forward.
+ *   qtype .. clip_hi : the activation quantizer, as qvit_quant_backward (QVIT_QT_LINEAR / QVIT_QT_NONLINEAR).
+ *   grad_y   : fp32 [rows][ldg];  grad_x : fp32 [rows][ldo], may be grad_y itself (then ldo == ldg).
+ *   grad_gamma, grad_beta : fp32 [cols], sum over rows of gy * xhat and of gy (gy: the quantizer backward's grad_x at
+ *              y = LayerNorm(x), xhat the normalized row); either may be NULL, and that reduction is skipped.
+ *   grad_scalars : [3] for d_quant, q_m, t_quant: definitions, masks and NaN behaviour of qvit_quant_backward at y.
+ *   y is recomputed with the operations of the forward in the same order, so every mask and rne(q) refers to the
+ *   value the forward quantized. A NaN in grad_y reaches the scalar sums and only its own row of grad_x.
+ *   workspace : qvit_layernorm_quant_backward_workspace_bytes(rows, cols) bytes, 16-byte aligned: one partial per
+ *              workgroup, folded in a fixed order by a second launch (no float atomics: bitwise
+ *              reproducible). The query returns QVIT_EINVAL for a negative size.
+ * Fast path only: cols % 4 == 0, cols <= 2048, ldx, ldg, ldo % 4 == 0, x / gamma / beta / grad_y / grad_x 16-byte
+ * aligned; anything else is QVIT_EALIGN and nothing is written (callers run the separate ops). rows == 0 writes zeros
+ * to the sums. Columns [cols, ld*) are never touched. Moves 3 rows cols 4 bytes plus the partials.
+ *
+ * qvit_gelu_quant_i8: codes = quantize(GELU(h)), byte for byte qvit_quantize_act_i8(qvit_gelu_f32(h)); arguments as
+ * qvit_quantize_act_i8.
+ *
+ * qvit_gelu_quant_backward: qvit_quant_backward at a = GELU(h) followed by GELU's own derivative:
+ * grad_h = (Phi(h) + h phi(h)) gy with Phi from the forward's erf; grad_scalars, workspace, alignment, aliasing
+ * (grad_h may be grad_y) and n == 0 as qvit_quant_backward. Moves 3 n 4 bytes.
+ */
+int64_t qvit_layernorm_quant_backward_workspace_bytes(int64_t rows, int64_t cols);
+int qvit_layernorm_quant_backward(const float* x, int64_t rows, int64_t cols, int64_t ldx,
+                                  const float* gamma, const float* beta, float eps,
+                                  int qtype, const float* d_quant, const float* q_m, const float* t_quant,
+                                  float clip_lo, float clip_hi,
+                                  const float* grad_y, int64_t ldg, float* grad_x, int64_t ldo,
+                                  float* grad_gamma, float* grad_beta, float* grad_scalars /* [3] */,
+                                  void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int qvit_gelu_quant_i8(const float* h, int64_t rows, int64_t cols, int64_t ldh, int qtype,
+                       const float* d_quant, const float* q_m, const float* t_quant, int levels,
+                       int8_t* codes, int64_t ldc, int64_t kpad, hipStream_t stream);
+int64_t qvit_gelu_quant_backward_workspace_bytes(int64_t n);
+int qvit_gelu_quant_backward(const float* h, const float* grad_y, int64_t n, int qtype,
+                             const float* d_quant, const float* q_m, const float* t_quant,
+                             float clip_lo, float clip_hi, float* grad_h, float* grad_scalars /* [3] */,
+                             void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/*
  * Weight quantizer + GEMM operand packing (QuantizeMixin.quantize_weight, quant_layers.py:332-354).
  *   w      : fp32 [n][ldw], first k columns used (nn.Linear weight [out,in]; a conv weight
  *            [Cout,Cin,kh,kw] is passed as [Cout][Cin*kh*kw]).

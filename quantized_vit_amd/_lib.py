@@ -60,6 +60,10 @@ _SIGNATURES = {
     "qvit_fake_quant_f32": [_c_p, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
     "qvit_quant_backward": [_c_p, _c_p, _i64, _i32, _c_p, _c_p, _c_p, _f32, _f32, _f32, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_gelu_f32": [_c_p, _i64, _c_p, _c_p],
+    "qvit_layernorm_quant_backward": [_c_p, _i64, _i64, _i64, _c_p, _c_p, _f32, _i32, _c_p, _c_p, _c_p, _f32, _f32,
+                                      _c_p, _i64, _c_p, _i64, _c_p, _c_p, _c_p, _c_p, _i64, _c_p],
+    "qvit_gelu_quant_i8": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i64, _c_p],
+    "qvit_gelu_quant_backward": [_c_p, _c_p, _i64, _i32, _c_p, _c_p, _c_p, _f32, _f32, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_pack_weight": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i64, _c_p, _c_p],
     "qvit_pad_bias": [_c_p, _i64, _c_p, _i64, _c_p],
     "qvit_pack_weight_w4r": [_c_p, _i64, _i64, _c_p, _c_p],
@@ -110,6 +114,8 @@ _SIGNATURES = {
 # name -> argtypes of the entry points returning int64_t
 INT64_FUNCS = {
     "qvit_quant_backward_workspace_bytes": [_i64],
+    "qvit_layernorm_quant_backward_workspace_bytes": [_i64, _i64],
+    "qvit_gelu_quant_backward_workspace_bytes": [_i64],
     "qvit_attention_backward_workspace_bytes": [_i64, _i64, _i64],
     "qvit_gemm_wgrad_workspace_bytes": [_i64, _i64, _i64],
 }
@@ -255,6 +261,92 @@ def gelu_f32(x: torch.Tensor) -> torch.Tensor:
     y = torch.empty_like(xc)
     _check(load().qvit_gelu_f32(_ptr(xc), xc.numel(), _ptr(y), _stream(x.device)), "qvit_gelu_f32")
     return y
+
+
+LN_BWD_MAX_COLS = 2048   # train_fuse.hip kLnMaxCols: a row of the LayerNorm backward stays in one wave's registers
+
+
+def _rows_ok(t: torch.Tensor) -> bool:
+    """fp32 device rows the train-fusion kernels take: unit column stride, row stride % 4, 16-byte base."""
+    return (t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.stride(1) == 1 and t.stride(0) % 4 == 0
+            and t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0)
+
+
+def layernorm_quant_backward_fits(x2d: torch.Tensor, gamma: Optional[torch.Tensor],
+                                  beta: Optional[torch.Tensor]) -> bool:
+    """Whether qvit_layernorm_quant_backward takes these rows (its alignment rules; else QVIT_EALIGN)."""
+    cols = x2d.shape[1] if x2d.dim() == 2 else 0
+    vec = lambda v: (v is not None and v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()
+                     and v.numel() == cols and v.data_ptr() % 16 == 0)
+    return _rows_ok(x2d) and cols % 4 == 0 and 0 < cols <= LN_BWD_MAX_COLS and vec(gamma) and vec(beta)
+
+
+def layernorm_quant_backward(x2d: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, qtype: int,
+                             d: torch.Tensor, qm: torch.Tensor, t: Optional[torch.Tensor], clip_lo: float,
+                             clip_hi: float, grad_y: torch.Tensor, grad_x: Optional[torch.Tensor] = None,
+                             want_gamma: bool = True, want_beta: bool = True):
+    """Backward of layernorm_quant_i8 (qvit_layernorm_quant_backward): x2d the LayerNorm input [rows, cols], grad_y
+    the gradient with respect to the quantizer's output. Returns (grad_x, grad_gamma, grad_beta, scalars): grad_x
+    [rows, cols] (written into `grad_x` when given; it may be grad_y itself), the affine gradients (None where not
+    wanted: that reduction is skipped) and the float32 [3] sums for d_quant, q_m, t_quant, all on the device."""
+    _require_gpu(x2d, "input")
+    _require_gpu(grad_y, "grad_y")
+    assert x2d.dtype == torch.float32 and grad_y.dtype == torch.float32 and x2d.dim() == 2
+    assert x2d.stride(1) == 1 and grad_y.stride(1) == 1 and tuple(grad_y.shape) == tuple(x2d.shape)
+    rows, cols = x2d.shape
+    if grad_x is None:
+        grad_x = torch.empty((rows, cols), dtype=torch.float32, device=x2d.device)
+    assert grad_x.is_cuda and grad_x.dtype == torch.float32 and grad_x.stride(1) == 1 and \
+        tuple(grad_x.shape) == (rows, cols)
+    lib = load()
+    nbytes = int(lib.qvit_layernorm_quant_backward_workspace_bytes(rows, cols))
+    if nbytes < 0:
+        _check(nbytes, "qvit_layernorm_quant_backward_workspace_bytes")
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=x2d.device)
+    gg = torch.empty(cols, dtype=torch.float32, device=x2d.device) if want_gamma else None
+    gb = torch.empty(cols, dtype=torch.float32, device=x2d.device) if want_beta else None
+    scalars = torch.empty(3, dtype=torch.float32, device=x2d.device)
+    _check(lib.qvit_layernorm_quant_backward(_ptr(x2d), rows, cols, x2d.stride(0), _ptr(gamma), _ptr(beta),
+                                             float(eps), qtype, _ptr(d), _ptr(qm), _ptr(t), float(clip_lo),
+                                             float(clip_hi), _ptr(grad_y), grad_y.stride(0), _ptr(grad_x),
+                                             grad_x.stride(0), _ptr(gg), _ptr(gb), _ptr(scalars), _ptr(ws),
+                                             ws.numel() * 8, _stream(x2d.device)), "qvit_layernorm_quant_backward")
+    return grad_x, gg, gb, scalars
+
+
+def gelu_quant_i8(h2d: torch.Tensor, qtype: int, d: Optional[torch.Tensor], qm: Optional[torch.Tensor],
+                  t: Optional[torch.Tensor], levels: int, out: torch.Tensor, kpad: int) -> torch.Tensor:
+    """codes = quantize(GELU(h)) (qvit_gelu_quant_i8): quantize_act_i8(gelu_f32(h)) byte for byte, in one pass."""
+    _require_gpu(h2d, "input")
+    assert h2d.dtype == torch.float32 and h2d.dim() == 2 and h2d.stride(1) == 1
+    rows, cols = h2d.shape
+    _check(load().qvit_gelu_quant_i8(_ptr(h2d), rows, cols, h2d.stride(0), qtype, _ptr(d), _ptr(qm), _ptr(t), levels,
+                                     _ptr(out), out.stride(0), kpad, _stream(h2d.device)), "qvit_gelu_quant_i8")
+    return out
+
+
+def gelu_quant_backward(h: torch.Tensor, grad_y: torch.Tensor, qtype: int, d: torch.Tensor, qm: torch.Tensor,
+                        t: Optional[torch.Tensor], clip_lo: float, clip_hi: float,
+                        grad_h: Optional[torch.Tensor] = None):
+    """Backward of gelu_quant_i8 (qvit_gelu_quant_backward) over contiguous h: (grad_h, scalars) as quant_backward
+    (grad_h may be grad_y itself)."""
+    _require_gpu(h, "input")
+    _require_gpu(grad_y, "grad_y")
+    assert h.dtype == torch.float32 and grad_y.dtype == torch.float32 and h.is_contiguous() and \
+        grad_y.is_contiguous() and h.numel() == grad_y.numel()
+    if grad_h is None:
+        grad_h = torch.empty_like(h)
+    assert grad_h.is_cuda and grad_h.dtype == torch.float32 and grad_h.is_contiguous() and \
+        grad_h.numel() == h.numel()
+    n = h.numel()
+    lib = load()
+    nbytes = int(lib.qvit_gelu_quant_backward_workspace_bytes(n))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=h.device)
+    scalars = torch.empty(3, dtype=torch.float32, device=h.device)
+    _check(lib.qvit_gelu_quant_backward(_ptr(h), _ptr(grad_y), n, qtype, _ptr(d), _ptr(qm), _ptr(t), float(clip_lo),
+                                        float(clip_hi), _ptr(grad_h), _ptr(scalars), _ptr(ws), nbytes,
+                                        _stream(h.device)), "qvit_gelu_quant_backward")
+    return grad_h, scalars
 
 
 def pack_weight(w2d: torch.Tensor, qtype: int, d: torch.Tensor, qm: torch.Tensor, t: Optional[torch.Tensor],

@@ -67,3 +67,42 @@ QVIT_DEV void ln_quant_row(const float4 (&v)[NV], int lane, int cols, float eps,
     }
   }
 }
+
+// The row's statistics and LayerNorm values for a backward pass that has to see what ln_quant_row quantized:
+// the same operations in the same order (sums, wave reduction, mean, masked squared deviations, rstd, and
+// y = (x - mean) * rstd * gamma + beta written as the same expression), so y[i] is bit for bit the value whose
+// code the forward stored. xhat[i] = (x - mean) * rstd is the normalized row the LayerNorm backward needs.
+// Lanes past the row (4 (lane + 64 i) >= cols) get zeros.
+template <int NV, class GB>
+QVIT_DEV void ln_row_values(const float4 (&v)[NV], int lane, int cols, float eps, GB gb, float& mean, float& rstd,
+                            float4 (&xhat)[NV], float4 (&y)[NV]) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+  mean = wave_sum_fast(s) / (float)cols;
+  float s2 = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = 4 * (lane + 64 * i);
+    if (c < cols) {
+      const float a = v[i].x - mean, b = v[i].y - mean, cc = v[i].z - mean, dd = v[i].w - mean;
+      s2 += (a * a + b * b) + (cc * cc + dd * dd);
+    }
+  }
+  const float var = wave_sum_fast(s2) / (float)cols;
+  rstd = 1.0f / sqrtf(var + eps);
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = 4 * (lane + 64 * i);
+    xhat[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    y[i] = xhat[i];
+    if (c < cols) {
+      float4 gv, bv;
+      gb(i, gv, bv);
+      y[i] = make_float4((v[i].x - mean) * rstd * gv.x + bv.x, (v[i].y - mean) * rstd * gv.y + bv.y,
+                         (v[i].z - mean) * rstd * gv.z + bv.z, (v[i].w - mean) * rstd * gv.w + bv.w);
+      xhat[i] = make_float4((v[i].x - mean) * rstd, (v[i].y - mean) * rstd, (v[i].z - mean) * rstd,
+                            (v[i].w - mean) * rstd);
+    }
+  }
+}

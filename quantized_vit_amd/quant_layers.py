@@ -706,9 +706,17 @@ class QuantizeMixin:
             grad_w, scal = _lib.quant_backward(wf, grad_wq, plan.qtype, plan.d_wt, plan.qm_wt, plan.t_wt,
                                                self.weight_clip_val[0], self.weight_clip_val[1], grad_x=grad_wq)
             quantizers.append(("wt", scal))
+        scalars = self._checked_scalars(plan, quantizers)
+        out = [grad_x.view_as(x).to(x.dtype) if need_x else None,
+               grad_w.view_as(weight).to(weight.dtype) if need_w else None,
+               grad_b]
+        return tuple(out) + self._scalar_grads(scalars, needs[3:9])
+
+    def _checked_scalars(self, plan: QuantPlan, quantizers: list) -> dict:
+        """{which: device scalars} of the quantizer backwards that ran, after the one host readback behind both
+        quantizers' NaN checks (:108-123 grad_t, :190-204 grad_d)."""
         scalars = {}
         if quantizers:
-            # one readback for both quantizers' NaN checks (:108-123 grad_t, :190-204 grad_d)
             host = torch.cat([sc for _, sc in quantizers]).cpu().tolist()
             chk = 2 if plan.qtype == _lib.QT_NONLINEAR else 0
             for i, (which, sc) in enumerate(quantizers):
@@ -719,10 +727,13 @@ class QuantizeMixin:
                     raise NanInGradientError(_nan_message(
                         f"{type(self).__name__} {which} quantizer, {'grad_t' if chk else 'grad_d'}",
                         ("d", "q_m", "t"), params, h))
-        out = [grad_x.view_as(x).to(x.dtype) if need_x else None,
-               grad_w.view_as(weight).to(weight.dtype) if need_w else None,
-               grad_b]
-        for j, which in ((3, "wt"), (6, "act")):
+        return scalars
+
+    def _scalar_grads(self, scalars: dict, needs: tuple) -> tuple:
+        """Gradients of (d_quant_wt, q_m_wt, t_quant_wt, d_quant_act, q_m_act, t_quant_act) shaped as the
+        parameters; None where `needs` (six flags, that order) is false."""
+        out = []
+        for j, which in ((0, "wt"), (3, "act")):
             for i, name in enumerate(("d_quant", "q_m", "t_quant")):
                 p = getattr(self, f"{name}_{which}", None)
                 out.append(scalars[which][i:i + 1].reshape(p.shape).to(p.dtype) if needs[j + i] else None)
@@ -924,22 +935,64 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
         M = G2.shape[0]
         grad_xq, grad_wq = self._gemm_grads(plan, tuple(xf.shape), None if hip_w else x_q, None if hip_x else w_q, G)
         if hip_x:
-            # G @ (d_wt k_w): qvit_gemm_wonly on the transposed codes (rows = in-features, reduction = out-features)
-            packed_t, npad_t, kpad_t = plan.packed_t()
-            Gp = G2
-            if G2.shape[1] != kpad_t or G2.stride(0) % 4 or G2.data_ptr() % 16:
-                Gp = torch.zeros((M, kpad_t), dtype=torch.float32, device=G2.device)
-                Gp[:, :plan.n] = G2
-            ldy = _round_up(plan.k, 4)
-            y = torch.empty((M, ldy), dtype=torch.float32, device=G2.device)
-            if M:
-                _lib.gemm_wonly(Gp, M, kpad_t, packed_t, plan.wfmt, plan.k, npad_t, plan.d_wt, None, y)
-            grad_xq = y if ldy == plan.k else y[:, :plan.k].contiguous()
+            grad_xq = self._dgrad_hip(plan, G2)
         if hip_w:
             # G^T @ (d_act codes): the int8 codes the forward contracted (the same quant_code)
             x2 = xf.reshape(-1, plan.k)
             grad_wq = _lib.gemm_wgrad(G2, self._act_codes(x2, plan), plan.k, plan.d_act)
         return grad_xq, grad_wq
+
+    def _dgrad_hip(self, plan: QuantPlan, G2: torch.Tensor) -> torch.Tensor:
+        """G2 @ (d_wt k_w), contiguous [M, k]: qvit_gemm_wonly on the transposed codes (rows = in-features,
+        reduction = out-features)."""
+        M = G2.shape[0]
+        packed_t, npad_t, kpad_t = plan.packed_t()
+        Gp = G2
+        if G2.shape[1] != kpad_t or G2.stride(0) % 4 or G2.data_ptr() % 16:
+            Gp = torch.zeros((M, kpad_t), dtype=torch.float32, device=G2.device)
+            Gp[:, :plan.n] = G2
+        ldy = _round_up(plan.k, 4)
+        y = torch.empty((M, ldy), dtype=torch.float32, device=G2.device)
+        if M:
+            _lib.gemm_wonly(Gp, M, kpad_t, packed_t, plan.wfmt, plan.k, npad_t, plan.d_wt, None, y)
+        return y if ldy == plan.k else y[:, :plan.k].contiguous()
+
+    def _backward_preop(self, plan: QuantPlan, eps: Optional[float], x: torch.Tensor, gamma, beta,
+                        weight: torch.Tensor, codes: torch.Tensor, G: torch.Tensor, needs: tuple) -> tuple:
+        """Backward of _PreOpLinearFunction: gradients for (x, gamma, beta, weight, bias, d_quant_wt, q_m_wt,
+        t_quant_wt, d_quant_act, q_m_act, t_quant_act); None where `needs` is false (that work is skipped). The
+        pre-op is LayerNorm (eps given) or GELU (eps None); `codes` are the forward's activation codes."""
+        need_x, need_g, need_bt, need_w, need_b = needs[:5]
+        need_wq = need_w or any(needs[5:8])                        # wgrad and the weight quantizer's backward run
+        need_pre = need_x or need_g or need_bt or any(needs[8:11])   # dgrad and the fused pre-op backward run
+        G2 = G.detach().float().reshape(-1, plan.n).contiguous()
+        grad_b = G2.sum(0).to(self.bias.dtype) if need_b else None
+        quantizers = []   # (which, device scalars), in the order of _backward_plan
+        grad_x = grad_g = grad_bt = None
+        if need_pre:
+            grad_xq = self._dgrad_hip(plan, G2)
+            x2 = x.detach().reshape(-1, plan.k)
+            qargs = (plan.qtype, plan.d_act, plan.qm_act, plan.t_act, self.act_clip_val[0], self.act_clip_val[1])
+            if eps is not None:
+                grad_x, grad_g, grad_bt, scal = _lib.layernorm_quant_backward(
+                    x2, gamma.detach(), beta.detach(), eps, *qargs, grad_y=grad_xq, grad_x=grad_xq,
+                    want_gamma=need_g, want_beta=need_bt)
+            else:
+                grad_x, scal = _lib.gelu_quant_backward(x2, grad_xq, *qargs, grad_h=grad_xq)
+            quantizers.append(("act", scal))
+        grad_w = None
+        if need_wq:
+            grad_wq = _lib.gemm_wgrad(G2, codes, plan.k, plan.d_act)
+            wf = weight.detach().float().contiguous()
+            grad_w, scal = _lib.quant_backward(wf, grad_wq, plan.qtype, plan.d_wt, plan.qm_wt, plan.t_wt,
+                                               self.weight_clip_val[0], self.weight_clip_val[1], grad_x=grad_wq)
+            quantizers.append(("wt", scal))
+        scalars = self._checked_scalars(plan, quantizers)
+        return (grad_x.view_as(x).to(x.dtype) if need_x else None,
+                grad_g.to(gamma.dtype) if need_g else None,
+                grad_bt.to(beta.dtype) if need_bt else None,
+                grad_w.view_as(weight).to(weight.dtype) if need_w else None,
+                grad_b) + self._scalar_grads(scalars, needs[5:11])
 
     def _forward_plan(self, input_: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
         if plan.int_path:
@@ -960,6 +1013,92 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
         x = self.quantize_act(input_.float()) if self.quant_mode == QuantizationMode.WEIGHT_AND_ACTIVATION \
             else input_.float()
         return F.linear(x.detach(), self.w_fakequant(plan), None if self.bias is None else self.bias.detach())
+
+
+# ---- train-time fusion: LayerNorm / GELU feeding a QuantizeLinear as one autograd node -------------------------
+# layer(norm(x)) and layer(gelu(h)) under autograd, without the fp32 tensor between the two modules: the forward
+# writes the layer's int8 activation codes straight from the pre-op's input (qvit_layernorm_quant_i8 /
+# qvit_gelu_quant_i8, the kernels of the inference pipeline) and keeps them for wgrad; the backward runs dgrad,
+# then one kernel for quantizer backward + pre-op backward (qvit_layernorm_quant_backward /
+# qvit_gelu_quant_backward). The codes come from the kernels' own LayerNorm / GELU values, which can differ from
+# torch's in the last bit, so a code at a rounding tie can differ from the modules route's.
+def _preop_plan(layer) -> Optional[QuantPlan]:
+    """The layer's plan if the fused nodes can run it: integer-path QuantizeLinear, weight + activation mode,
+    linear or nonlinear quantizer, both backward GEMMs on the HIP kernels."""
+    if not isinstance(layer, QuantizeLinear) or layer.quant_mode != QuantizationMode.WEIGHT_AND_ACTIVATION:
+        return None
+    if layer.quant_type not in (QuantizationType.SYMMETRIC_LINEAR, QuantizationType.SYMMETRIC_NONLINEAR):
+        return None
+    if set(_backward_gemm_ops()) != {"dgrad", "wgrad"}:
+        return None
+    plan = layer.quant_plan()
+    return plan if plan.int_path and "pack_t" in plan.extra and plan.k % 4 == 0 else None
+
+
+class _PreOpLinearFunction(torch.autograd.Function):
+    """codes = quantize(pre(x)); out = contraction(codes): pre = LayerNorm (eps given) or GELU (eps None). Saves
+    the pre-op's input and the int8 codes."""
+
+    @staticmethod
+    def forward(ctx, layer, plan, eps, x, gamma, beta, weight, bias, d_wt, qm_wt, t_wt, d_act, qm_act, t_act):
+        x2 = x.detach().reshape(-1, plan.k)
+        M = x2.shape[0]
+        codes = torch.empty((M, plan.kpad), dtype=torch.int8, device=x2.device)
+        if eps is not None:
+            _lib.layernorm_quant_i8(x2, gamma.detach(), beta.detach(), eps, plan.qtype, plan.d_act, plan.qm_act,
+                                    plan.t_act, 0, codes, plan.kpad)
+        else:
+            _lib.gelu_quant_i8(x2, plan.qtype, plan.d_act, plan.qm_act, plan.t_act, 0, codes, plan.kpad)
+        trace_codes(layer, codes, plan.k)
+        out = layer.gemm_codes(codes, plan, _lib.EPI_F32)
+        if out.shape[1] != plan.n:
+            out = out[:, :plan.n].contiguous()
+        ctx.layer, ctx.plan, ctx.eps = layer, plan, eps
+        ctx.save_for_backward(x, gamma, beta, weight, codes)
+        return out.view(*x.shape[:-1], plan.n)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        x, gamma, beta, weight, codes = ctx.saved_tensors
+        grads = ctx.layer._backward_preop(ctx.plan, ctx.eps, x, gamma, beta, weight, codes, grad_output,
+                                          tuple(ctx.needs_input_grad[3:]))
+        return (None, None, None) + grads
+
+
+def _preop_apply(layer, plan, eps, x, gamma, beta):
+    g = lambda n: getattr(layer, n, None)
+    return _PreOpLinearFunction.apply(layer, plan, eps, x, gamma, beta, layer.weight, layer.bias, g("d_quant_wt"),
+                                      g("q_m_wt"), g("t_quant_wt"), g("d_quant_act"), g("q_m_act"),
+                                      g("t_quant_act"))
+
+
+def _preop_input_ok(x: torch.Tensor, plan: QuantPlan) -> bool:
+    return (x.is_cuda and x.dtype == torch.float32 and x.dim() >= 2 and x.shape[-1] == plan.k
+            and x.numel() > 0 and x.is_contiguous() and x.data_ptr() % 16 == 0)
+
+
+def layernorm_linear(norm: nn.LayerNorm, layer: "QuantizeLinear", x: torch.Tensor) -> torch.Tensor:
+    """layer(norm(x)). With autograd live and an eligible pair (see _preop_plan; an affine LayerNorm over the last
+    dimension; the alignment rules of qvit_layernorm_quant_backward) this is one autograd node that never forms
+    norm(x) in fp32; otherwise the two modules are composed as they are."""
+    plan = _preop_plan(layer) if torch.is_grad_enabled() else None
+    if (plan is not None and isinstance(norm, nn.LayerNorm) and norm.elementwise_affine and norm.bias is not None
+            and tuple(norm.normalized_shape) == (plan.k,) and _preop_input_ok(x, plan)
+            and (_autograd_live(layer, x) or _autograd_live(norm, x))
+            and _lib.layernorm_quant_backward_fits(x.detach().reshape(-1, plan.k), norm.weight.detach(),
+                                                   norm.bias.detach())):
+        return _preop_apply(layer, plan, float(norm.eps), x, norm.weight, norm.bias)
+    return layer(norm(x))
+
+
+def gelu_linear(layer: "QuantizeLinear", h: torch.Tensor, act: Optional[nn.Module] = None) -> torch.Tensor:
+    """layer(gelu(h)) for the exact GELU (`act`, when given, must be nn.GELU(approximate="none")), as one autograd
+    node when the pair is eligible (see layernorm_linear); otherwise the modules are composed as they are."""
+    exact = act is None or (isinstance(act, nn.GELU) and act.approximate == "none")
+    plan = _preop_plan(layer) if torch.is_grad_enabled() and exact else None
+    if plan is not None and _preop_input_ok(h, plan) and _autograd_live(layer, h):
+        return _preop_apply(layer, plan, None, h, None, None)
+    return layer(F.gelu(h) if act is None else act(h))
 
 
 class QuantizeConv2d(nn.Conv2d, QuantizeMixin):

@@ -46,6 +46,12 @@ FUSE_RESID_LN = os.environ.get("QVIT_FUSE_LN", "0") == "1"
 # full-range random codes but 2-3 % slower on the model's own activations, and its LayerNorm 4 % slower
 # (profiles/r05_fc1_weight_stationary_ab.txt).
 FC1_WEIGHT_STATIONARY = os.environ.get("QVIT_FC1_A32", "0") == "1"
+# Under autograd, a Block runs norm1 -> qkv, norm2 -> fc1 and GELU -> fc2 as one autograd node each
+# (quant_layers.layernorm_linear / gelu_linear: no fp32 LayerNorm / GELU output is formed or saved, the backward is
+# one fused HIP kernel per site) when QVIT_TRAIN_FUSE=1 (or TRAIN_FUSE = True). Off by default: the fused forward
+# quantizes the kernels' own LayerNorm / GELU values, which can differ from torch's in the last bit, so a code at a
+# rounding tie can differ from the modules route's.
+TRAIN_FUSE = os.environ.get("QVIT_TRAIN_FUSE", "0") == "1"
 
 # Benchmark instrumentation: when KERNEL_TIMING[name] is a list (name in "fc1", "fc2", "proj",
 # "qkv_attn", "ln"), the fused block appends a (start, end) HIP event pair recorded on the launch
@@ -452,9 +458,25 @@ class Block(nn.Module):
             m.fc2.gemm_codes(hid, p_fc2, _lib.EPI_F32_RESID, out=x2)
         return x, None
 
+    def forward_train_fused(self, x: torch.Tensor) -> torch.Tensor:
+        """The modules route with the three LayerNorm / GELU -> QuantizeLinear sites as fused autograd nodes
+        (TRAIN_FUSE); the attention core, the dropouts and the residual adds are the modules' own."""
+        a, m = self.attn, self.mlp
+        B, N, _ = x.shape
+        y = a.core(_ql.layernorm_linear(self.norm1, a.qkv, x), B, N)
+        x = x + self.drop_path(a.proj_drop(a.proj(y)))
+        h = _ql.layernorm_linear(self.norm2, m.fc1, x)
+        if _inactive(m.drop):   # nothing between GELU and fc2
+            y = _ql.gelu_linear(m.fc2, h, m.act)
+        else:
+            y = m.fc2(m.drop(m.act(h)))
+        return x + self.drop_path(m.drop(y))
+
     def forward(self, x):
         if self.fused_ok(x):
             return self.forward_fused_(x.contiguous().clone())
+        if TRAIN_FUSE and x.dim() == 3 and _autograd_live(self, x):
+            return self.forward_train_fused(x)
         x = x + self.drop_path(self.attn(self.norm1(x)))
         x = x + self.drop_path(self.mlp(self.norm2(x)))
         return x
