@@ -12,8 +12,10 @@ import math
 import pytest
 import torch
 
+import vit_codes_ref as V
 from oracle import quant_oracle as O
 from quantized_vit_amd import _lib
+from ultra_ref import assert_codes_tie_proven
 
 pytestmark = pytest.mark.gpu
 
@@ -118,6 +120,9 @@ def test_attention_int8_codes_vs_oracle(dev, qt, t):
     diff = (got - want).abs()
     assert diff.max().item() <= 1
     assert (diff > 0).float().mean().item() <= 1e-3
+    c = V.attention_code_case(qt, t)      # every differing code is a possible tie within 2e-6 max|out| of fp64
+    assert torch.equal(c.qkv, qkv)
+    assert_codes_tie_proven(got, c.ref, c.tie, c.cap)
 
 
 def test_attention_argument_validation(dev):
@@ -179,6 +184,9 @@ def test_attention_split_int8_and_in_scale(dev):
     b = run_split(dev, B, N, H, qkv, 0.125, mode=_lib.ATT_I8, in_scale=2.0 ** -2, **kw)
     assert torch.equal(a, b)
     assert len(torch.unique(b)) > 50
+    c = V.attention_split_case()
+    assert torch.equal(c.qkv, qkv)
+    assert_codes_tie_proven(b, c.ref, c.tie, c.cap)
 
 
 @pytest.mark.parametrize("wfmt", [_lib.W4, _lib.W8])
@@ -327,6 +335,8 @@ def test_qkv_attention_fused_int8_codes(dev, B, N, H):
     assert diff.max().item() <= 1
     assert (diff > 0).float().mean().item() <= 1e-3
     assert len(torch.unique(ref)) > 60
+    c = V.fused_attention_case(B, N, H, 7 + N)     # fp64 attention of the fp64 projection, not the split path
+    assert_codes_tie_proven(out, c.ref, c.tie, c.cap)
 
 
 # known answer: zero weights, q bias -30, k bias +30, so every score of a row is the same large negative
@@ -381,6 +391,8 @@ def test_qkv_attention_fused_int8_store_paths(dev, use_table, pad):
     assert diff.max().item() <= 1
     assert (diff > 0).float().mean().item() <= 1e-3
     assert len(torch.unique(ref)) > 60
+    c = V.fused_attention_case(B, N, H, 11 + pad)
+    assert_codes_tie_proven(out, c.ref, c.tie, c.cap)
     if pad:
         assert (big[:, C:].cpu() == 99).all()
 
