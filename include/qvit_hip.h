@@ -616,6 +616,23 @@ int qvit_qkv_attention(const int8_t* A, int64_t B, int64_t N, int64_t K, int64_t
                        int64_t ldo, int out_qtype, const float* out_d, const float* out_qm,
                        const float* out_t, int out_levels, const void* epi_table, hipStream_t stream);
 
+/*
+ * qvit_qkv_attention for the first NQ tokens of each image only (the class / distillation token rows the
+ * head of a classifier reads after the last block): K and V are projected for all N tokens, q and the
+ * attention only for query tile 0, with the block body and key-block order the full kernel uses for it.
+ *   NQ   : 1 <= NQ <= min(N, 32), else QVIT_EINVAL and nothing is launched;
+ *   out  : compact [B*NQ][ldo]; row b*NQ + i equals, bit for bit, row b*N + i of what qvit_qkv_attention
+ *          writes for the same arguments (both out modes, with and without epi_table). Columns >= H*64
+ *          and every other row are not written.
+ * Every other argument as qvit_qkv_attention.
+ */
+int qvit_qkv_attention_q(const int8_t* A, int64_t B, int64_t N, int64_t NQ, int64_t K, int64_t lda,
+                         const void* Wp, int wfmt, int64_t npad, const float* d_act, const float* d_wt,
+                         const float* bias, int64_t H, int64_t head_dim, float scale, float in_scale,
+                         int out_mode, void* out, int64_t ldo, int out_qtype, const float* out_d,
+                         const float* out_qm, const float* out_t, int out_levels, const void* epi_table,
+                         hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -106,6 +106,8 @@ _SIGNATURES = {
                             _c_p, _c_p],
     "qvit_qkv_attention": [_c_p, _i64, _i64, _i64, _i64, _c_p, _i32, _i64, _c_p, _c_p, _c_p, _i64, _i64, _f32, _f32,
                            _i32, _c_p, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
+    "qvit_qkv_attention_q": [_c_p, _i64, _i64, _i64, _i64, _i64, _c_p, _i32, _i64, _c_p, _c_p, _c_p, _i64, _i64, _f32,
+                             _f32, _i32, _c_p, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
     "qvit_attention_split": [_c_p, _c_p, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _c_p, _i64, _i32, _c_p, _c_p,
                              _c_p, _i32, _c_p, _c_p],
     "qvit_attention_backward": [_c_p, _c_p, _c_p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _f32, _c_p,
@@ -758,6 +760,24 @@ def qkv_attention(codes: torch.Tensor, B: int, N: int, K: int, packed: torch.Ten
                                      _ptr(d_wt), _ptr(bias_pad), H, 64, scale, in_scale, out_mode, _ptr(out),
                                      out.stride(0), out_qtype, _ptr(out_d), _ptr(out_qm), _ptr(out_t), out_levels,
                                      _ptr(epi_table), _stream(codes.device)), "qvit_qkv_attention")
+    return out
+
+
+QKV_ATT_MAX_NQ = 32
+
+
+def qkv_attention_q(codes: torch.Tensor, B: int, N: int, NQ: int, K: int, packed: torch.Tensor, npad: int,
+                    d_act: torch.Tensor, d_wt: torch.Tensor, bias_pad: Optional[torch.Tensor], H: int, scale: float,
+                    out: torch.Tensor, out_mode: int = ATT_F32, in_scale: float = 1.0, out_qtype: int = 0,
+                    out_d=None, out_qm=None, out_t=None, out_levels: int = 0,
+                    epi_table: Optional[torch.Tensor] = None, wfmt: int = W4) -> torch.Tensor:
+    """qkv_attention for the first NQ <= 32 tokens of each image (qvit_qkv_attention_q): `out` is the compact
+    [B*NQ, ldo], its row b*NQ + i the same bits as row b*N + i of qkv_attention."""
+    _require_gpu(codes, "codes")
+    _check(load().qvit_qkv_attention_q(_ptr(codes), B, N, NQ, K, codes.stride(0), _ptr(packed), wfmt, npad,
+                                       _ptr(d_act), _ptr(d_wt), _ptr(bias_pad), H, 64, scale, in_scale, out_mode,
+                                       _ptr(out), out.stride(0), out_qtype, _ptr(out_d), _ptr(out_qm), _ptr(out_t),
+                                       out_levels, _ptr(epi_table), _stream(codes.device)), "qvit_qkv_attention_q")
     return out
 
 

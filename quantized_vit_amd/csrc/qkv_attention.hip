@@ -18,6 +18,11 @@
 //      order of the terms inside the q·k, P·V and row sums, and a running max kept an integer).
 // The next unit's first weight k-steps (ring) and activation k-steps (registers) load while the current
 // unit's attention runs. N <= 208.
+// Class-token arm (CLS, qvit_qkv_attention_q): only the first nq <= 32 queries of each image are wanted (the last
+// block of a classifier), so only rotated wave 0 projects q (its token tiles 0, 1, exactly as in the full kernel),
+// attends (query tile 0 over all key blocks, the same block body in the same order) and stores rows < nq to the
+// compact output [B * nq]; every other wave projects only the k and v features of its tiles and then waits at the
+// next unit's head. The loads, DMA pieces and barriers of every wave are those of the full kernel.
 #include "attn32.h"
 
 #include <algorithm>
@@ -63,12 +68,12 @@ QVIT_DEV v4i unpack16(uint2 p) {
 // NKC: the number of 64-deep k-steps when fixed at compile time (12: K = 768, the ViT-B qkv; ViT-L's
 // H * 64 = 1024 exceeds QKV_ATT_MAX_C and takes the split path), which unrolls the projection loop
 // completely; 0: K / 64 at run time (K % 256 == 0, e.g. 256, 512 or 1024 with <= 12 heads)
-template <int OUT, int NKC>
+template <int OUT, int NKC, bool CLS>
 __global__ __launch_bounds__(FT, 1) void qkv_attn_kernel(
     const int8_t* __restrict__ A, int K, int64_t lda, const int8_t* __restrict__ Wp, int npad,
     const float* __restrict__ d_act, const float* __restrict__ d_wt, const float* __restrict__ bias, int B, int N,
     int H, float scale, float in_scale, void* __restrict__ out, int64_t ldo, int out_qtype, const float* out_d,
-    const float* out_qm, const float* out_t, int out_levels, const int8_t* __restrict__ epi_table) {
+    const float* out_qm, const float* out_t, int out_levels, const int8_t* __restrict__ epi_table, int nq) {
   __shared__ __attribute__((aligned(16))) int8_t smem[LDS_TOTAL];
   int8_t* kv = smem;
   int8_t* wring = smem + KV_BYTES;
@@ -215,7 +220,11 @@ __global__ __launch_bounds__(FT, 1) void qkv_attn_kernel(
     const int nt = (tv[0] ? 1 : 0) + (tv[1] ? 1 : 0);
     // projection ranges of the wave's two tiles: 1 all fragments, 2 fragments 0 .. 5, 3 fragments 6 .. 11, 0 none
     const int pmode = (bal && wr == 7) ? 3 : (bal && (wr == 4 || wr == 5)) ? 2 : (nt == 2) ? 0 : 1;
-    const int prange[TPW] = {pmode == 3 ? 3 : 1, pmode == 0 ? 1 : pmode == 2 ? 2 : pmode == 3 ? 3 : 0};
+    // CLS: only rotated wave 0 (query tile 0) needs q; the others drop the q fragments of their ranges:
+    // 4 fragments 4 .. 11 (k and v), 5 fragments 4, 5 (the first half of k); range 3 has no q fragment
+    const bool qwave = !CLS || wr == 0;
+    const int prange[TPW] = {pmode == 3 ? 3 : qwave ? 1 : 4,
+                             pmode == 0 ? (qwave ? 1 : 4) : pmode == 2 ? (qwave ? 2 : 5) : pmode == 3 ? 3 : 0};
 
     // ---- 1. projection ---------------------------------------------------------------------------
     // unit head: everything issued before (the previous unit's output stores included) has landed, the
@@ -245,9 +254,11 @@ __global__ __launch_bounds__(FT, 1) void qkv_attn_kernel(
     // two activation loads go between the first fragments' MFMAs in that order (the next top's count).
     auto kstep = [&](auto r0, auto r1, int s, int q) __attribute__((always_inline)) {
       constexpr int R0 = decltype(r0)::value, R1 = decltype(r1)::value;
-      constexpr auto inr = [](int R, int f) constexpr { return R == 1 || (R == 2 && f < 6) || (R == 3 && f >= 6); };
+      constexpr auto inr = [](int R, int f) constexpr {
+        return R == 1 || (R == 2 && f < 6) || (R == 3 && f >= 6) || (R == 4 && f >= 4) || (R == 5 && (f == 4 || f == 5));
+      };
       constexpr auto used = [=](int f) constexpr { return inr(R0, f) || inr(R1, f); };
-      constexpr int F0 = (R0 == 3 && R1 != 1 && R1 != 2) ? 6 : 0;  // first fragment used
+      constexpr int F0 = (R0 == 3 && R1 != 1 && R1 != 2) ? 6 : (R0 == 4) ? 4 : 0;  // first fragment used
       __builtin_amdgcn_sched_barrier(0);
       if (q & 1) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(TOPCNT) : "memory");
       __builtin_amdgcn_sched_barrier(0);
@@ -260,7 +271,7 @@ __global__ __launch_bounds__(FT, 1) void qkv_attn_kernel(
         if (inr(R0, f)) acc[0][f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wc, xa[q][0], acc[0][f], 0, 0, 0);
         if (inr(R1, f)) acc[1][f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(wc, xa[q][1], acc[1][f], 0, 0, 0);
         if (f < 11 && used(f + 1)) wc = unpack16(wfr[f + 1]);
-        if (more) wfr[f] = wfrag(rn, f);
+        if (more && (!CLS || used(f))) wfr[f] = wfrag(rn, f);  // (CLS: the q fragments are read by the q wave only)
         if (f == 0 && (q & 1)) {  // weight k-steps s + 3, s + 4 (past the unit's end: the next unit's 0 .. 3)
 #pragma unroll
           for (int d = 3; d <= 4; ++d) {
@@ -284,8 +295,9 @@ __global__ __launch_bounds__(FT, 1) void qkv_attn_kernel(
     // (k-step 0's weight fragments are read inside each variant: values read before the branch would stay
     // live across both of its structurized arms)
     auto kloop = [&](auto r0, auto r1) __attribute__((always_inline)) {
+      constexpr int F0 = (CLS && decltype(r0)::value == 4) ? 4 : 0;
 #pragma unroll
-      for (int f = 0; f < 12; ++f) wfr[f] = wfrag(0, f);
+      for (int f = F0; f < 12; ++f) wfr[f] = wfrag(0, f);
       if constexpr (NKC > 0) {
 #pragma unroll
         for (int s = 0; s < NKC; s += 4) {
@@ -304,9 +316,18 @@ __global__ __launch_bounds__(FT, 1) void qkv_attn_kernel(
       }
     };
     using IC1 = std::integral_constant<int, 1>;
-    if (pmode == 0) kloop(IC1{}, IC1{});
-    else if (pmode == 2) kloop(IC1{}, std::integral_constant<int, 2>{});
-    else if (pmode == 3) kloop(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
+    using IC4 = std::integral_constant<int, 4>;
+    // CLS changes no load of any variant: every wave still issues its DMA pieces and its two activation loads per
+    // k-step at the same places (fragments 0, 2, 4 of the loop, MFMAs or not), so the counted vmcnt(TOPCNT) of
+    // each k-step top and the unit head's vmcnt(0) count exactly what they count in the full kernel
+    if (CLS && !qwave) {
+      if (pmode == 0) kloop(IC4{}, IC4{});
+      else if (pmode == 2) kloop(IC4{}, std::integral_constant<int, 5>{});
+      else if (pmode == 3) kloop(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
+      else kloop(IC4{}, std::integral_constant<int, 0>{});
+    } else if (pmode == 0) kloop(IC1{}, IC1{});
+    else if (!CLS && pmode == 2) kloop(IC1{}, std::integral_constant<int, 2>{});  // (wr = 4, 5, 7: never the q wave)
+    else if (!CLS && pmode == 3) kloop(std::integral_constant<int, 3>{}, std::integral_constant<int, 3>{});
     else kloop(IC1{}, std::integral_constant<int, 0>{});  // (a third, MFMA-free variant for nt == 0 spills)
     cur = nxt;
     unit_src(j + 2, nxt);
@@ -319,9 +340,14 @@ __global__ __launch_bounds__(FT, 1) void qkv_attn_kernel(
     for (int tt = 0; tt < TPW; ++tt) {
       const int row = 16 * ptile(wr, tt) + fr;  // token / key row of the images
       const bool pv = ptile(wr, tt) < ntile;     // (the projection's tile: wr = 7's are 9 and 11 when balanced)
-      const bool lo_half = prange[tt] == 1 || prange[tt] == 2, hi_half = prange[tt] == 1 || prange[tt] == 3;
+      const bool lo_half = prange[tt] == 1 || prange[tt] == 2 || (CLS && prange[tt] >= 4);
+      const bool hi_half = prange[tt] == 1 || prange[tt] == 3 || (CLS && prange[tt] == 4);
 #pragma unroll
       for (int p = 0; p < 3; ++p) {
+        if (CLS && p == 0 && !qwave) {  // no q: these waves do not attend
+          qh[tt][0] = qh[tt][1] = ql[tt][0] = ql[tt][1] = h8{};
+          continue;
+        }
         float x[16];
         const float4* bl = reinterpret_cast<const float4*>(bias_l + p * C + 64 * h + 16 * fq);
 #pragma unroll
@@ -397,7 +423,7 @@ __global__ __launch_bounds__(FT, 1) void qkv_attn_kernel(
     // With 7 key blocks (N 193 .. 224: ViT @ 224, N = 197) the block loop is straight-line code and every
     // LDS offset an immediate; otherwise two blocks per iteration with ping-pong score registers (no copy of
     // the loop-carried scores).
-    if (nt > 0) {
+    if (CLS ? qwave : nt > 0) {
       auto last = [&](int kb, const f16x& sc) __attribute__((always_inline)) {
         if (nfull < nkb) softmax_pv32<true, IMGF>(kv + kb * KB * 128, sc, m, l, o, voffs, kb * KB, N, sl2);
         else softmax_pv32<false, IMGF>(kv + kb * KB * 128, sc, m, l, o, voffs, kb * KB, N, sl2);
@@ -429,7 +455,12 @@ __global__ __launch_bounds__(FT, 1) void qkv_attn_kernel(
       }
     }
     sp.mark(0);
-    attend_store32<OUT>(tv, l, o, wr, N, b, h, in_scale, out, ldo, qp, tb, st16);
+    if constexpr (CLS) {
+      // the q wave (wr = 0: queries 0 .. 31) stores its first nq rows to the compact [B * nq] output
+      if (qwave) attend_store32<OUT>(tv, l, o, 0, nq, b, h, in_scale, out, ldo, qp, tb, st16);
+    } else {
+      attend_store32<OUT>(tv, l, o, wr, N, b, h, in_scale, out, ldo, qp, tb, st16);
+    }
     sp.mark(4);
   }
   sp.flush();
@@ -437,11 +468,13 @@ __global__ __launch_bounds__(FT, 1) void qkv_attn_kernel(
 
 }  // namespace
 
-extern "C" int qvit_qkv_attention(const int8_t* A, int64_t B, int64_t N, int64_t K, int64_t lda, const void* Wp,
-                                  int wfmt, int64_t npad, const float* d_act, const float* d_wt, const float* bias,
-                                  int64_t H, int64_t head_dim, float scale, float in_scale, int out_mode, void* out,
-                                  int64_t ldo, int out_qtype, const float* out_d, const float* out_qm,
-                                  const float* out_t, int out_levels, const void* epi_table, hipStream_t stream) {
+// NQ = 0: the full kernel (every query); 1 .. 32: the class-token arm
+static int qkv_attention_launch(const int8_t* A, int64_t B, int64_t N, int64_t K, int64_t lda, const void* Wp,
+                                int wfmt, int64_t npad, const float* d_act, const float* d_wt, const float* bias,
+                                int64_t H, int64_t head_dim, float scale, float in_scale, int out_mode, void* out,
+                                int64_t ldo, int out_qtype, const float* out_d, const float* out_qm,
+                                const float* out_t, int out_levels, const void* epi_table, int64_t NQ,
+                                hipStream_t stream) {
   if (!A || !Wp || !out || !d_act || !d_wt) return QVIT_ENULL;
   if (wfmt != QVIT_W4 || head_dim != 64) return QVIT_EINVAL;
   if (B < 0 || N <= 0 || N > MAXN || H <= 0 || K <= 0 || K % 256 || K > 65536 || lda < K) return QVIT_EINVAL;
@@ -472,19 +505,45 @@ extern "C" int qvit_qkv_attention(const int8_t* A, int64_t B, int64_t N, int64_t
   const int64_t grid = std::max<int64_t>(8, (int64_t)cus / 8 * 8);  // one workgroup per CU, a multiple of 8
   const int8_t* w = reinterpret_cast<const int8_t*>(Wp);
   const int8_t* tab = reinterpret_cast<const int8_t*>(epi_table);
-#define QVIT_QA_LAUNCH(OUTV, NKV, TAB)                                                                          \
-  hipLaunchKernelGGL((qkv_attn_kernel<OUTV, NKV>), dim3((unsigned)grid), dim3(FT), 0, stream, A, (int)K, lda, w,    \
-                     (int)npad, d_act, d_wt, bias, (int)B, (int)N, (int)H, scale, in_scale, out, ldo, out_qtype,   \
-                     out_d, out_qm, out_t, out_levels, TAB)
-  if (out_mode == QVIT_ATT_F32) {
-    if (K == 768) QVIT_QA_LAUNCH(0, 12, nullptr);
-    else QVIT_QA_LAUNCH(0, 0, nullptr);
-  } else {
-    if (K == 768) QVIT_QA_LAUNCH(1, 12, tab);
-    else QVIT_QA_LAUNCH(1, 0, tab);
-  }
+#define QVIT_QA_LAUNCH(OUTV, NKV, CLSV, TAB)                                                                     \
+  hipLaunchKernelGGL((qkv_attn_kernel<OUTV, NKV, CLSV>), dim3((unsigned)grid), dim3(FT), 0, stream, A, (int)K, lda, \
+                     w, (int)npad, d_act, d_wt, bias, (int)B, (int)N, (int)H, scale, in_scale, out, ldo, out_qtype, \
+                     out_d, out_qm, out_t, out_levels, TAB, (int)NQ)
+#define QVIT_QA_LAUNCH_K(OUTV, TAB)                                                                              \
+  do {                                                                                                           \
+    if (NQ > 0) {                                                                                                \
+      if (K == 768) QVIT_QA_LAUNCH(OUTV, 12, true, TAB);                                                         \
+      else QVIT_QA_LAUNCH(OUTV, 0, true, TAB);                                                                   \
+    } else {                                                                                                     \
+      if (K == 768) QVIT_QA_LAUNCH(OUTV, 12, false, TAB);                                                        \
+      else QVIT_QA_LAUNCH(OUTV, 0, false, TAB);                                                                  \
+    }                                                                                                            \
+  } while (0)
+  if (out_mode == QVIT_ATT_F32) QVIT_QA_LAUNCH_K(0, nullptr);
+  else QVIT_QA_LAUNCH_K(1, tab);
+#undef QVIT_QA_LAUNCH_K
 #undef QVIT_QA_LAUNCH
   return qvit_hip_status(hipGetLastError());
+}
+
+extern "C" int qvit_qkv_attention(const int8_t* A, int64_t B, int64_t N, int64_t K, int64_t lda, const void* Wp,
+                                  int wfmt, int64_t npad, const float* d_act, const float* d_wt, const float* bias,
+                                  int64_t H, int64_t head_dim, float scale, float in_scale, int out_mode, void* out,
+                                  int64_t ldo, int out_qtype, const float* out_d, const float* out_qm,
+                                  const float* out_t, int out_levels, const void* epi_table, hipStream_t stream) {
+  return qkv_attention_launch(A, B, N, K, lda, Wp, wfmt, npad, d_act, d_wt, bias, H, head_dim, scale, in_scale,
+                              out_mode, out, ldo, out_qtype, out_d, out_qm, out_t, out_levels, epi_table, 0, stream);
+}
+
+extern "C" int qvit_qkv_attention_q(const int8_t* A, int64_t B, int64_t N, int64_t NQ, int64_t K, int64_t lda,
+                                    const void* Wp, int wfmt, int64_t npad, const float* d_act, const float* d_wt,
+                                    const float* bias, int64_t H, int64_t head_dim, float scale, float in_scale,
+                                    int out_mode, void* out, int64_t ldo, int out_qtype, const float* out_d,
+                                    const float* out_qm, const float* out_t, int out_levels, const void* epi_table,
+                                    hipStream_t stream) {
+  if (NQ < 1 || NQ > 32 || NQ > N) return QVIT_EINVAL;
+  return qkv_attention_launch(A, B, N, K, lda, Wp, wfmt, npad, d_act, d_wt, bias, H, head_dim, scale, in_scale,
+                              out_mode, out, ldo, out_qtype, out_d, out_qm, out_t, out_levels, epi_table, NQ, stream);
 }
 
 QVIT_ATT_STAMP_READER(qvit_qkv_att_stamps)  // diag_stamps.h: -DQVIT_ATT_STAMPS builds only

@@ -52,10 +52,18 @@ FC1_WEIGHT_STATIONARY = os.environ.get("QVIT_FC1_A32", "0") == "1"
 # quantizes the kernels' own LayerNorm / GELU values, which can differ from torch's in the last bit, so a code at a
 # rounding tie can differ from the modules route's.
 TRAIN_FUSE = os.environ.get("QVIT_TRAIN_FUSE", "0") == "1"
+# The heads read only the class (and distillation) token rows of the last block, and everything after its attention
+# is row-independent, so the last fused block computes only those rows: qvit_qkv_attention_q (all keys and values, the
+# first num_tokens queries), then proj, norm2, fc1 and fc2 at M = B * num_tokens. The logits are bit-identical. On by
+# default; QVIT_CLS_PRUNE=0 (or LAST_BLOCK_CLS_ONLY = False) runs the whole last block, for A/B runs. Off while codes
+# are traced (quant_layers.CODE_TRACE), so parity reports keep seeing every row of every layer.
+LAST_BLOCK_CLS_ONLY = os.environ.get("QVIT_CLS_PRUNE", "1") != "0"
 
 # Benchmark instrumentation: when KERNEL_TIMING[name] is a list (name in "fc1", "fc2", "proj",
 # "qkv_attn", "ln"), the fused block appends a (start, end) HIP event pair recorded on the launch
 # stream (torch's current stream, which every _lib entry point launches on) around each such launch.
+# The class-token launches of the last block (LAST_BLOCK_CLS_ONLY) do other work per launch, so they are recorded
+# under names of their own ("qkv_attn_cls", "proj_cls", "ln_cls", "fc1_cls", "fc2_cls") and never under the above.
 KERNEL_TIMING: dict = {}
 
 
@@ -335,11 +343,46 @@ class Block(nn.Module):
                            p_next.kpad)
         return out
 
+    def _cls_tail_(self, x: torch.Tensor, cls_codes: torch.Tensor, nt: int):
+        """The rest of the last block (proj, norm2, fc1, fc2) on the first `nt` token rows of every image only:
+        `cls_codes` [B*nt, >= proj.kpad] are proj's activation codes of those rows (any row stride). nt = 1 updates
+        the class rows of the residual buffer in place through a strided view (row stride N*C) and returns x; nt > 1
+        gathers the rows into a compact buffer and returns it as [B, nt, C]. The other rows of x are left as they
+        were after the previous block: nothing downstream reads them."""
+        B, N, C = x.shape
+        a, m = self.attn, self.mlp
+        p_proj, p_fc1, p_fc2 = a.proj.quant_plan(), m.fc1.quant_plan(), m.fc2.quant_plan()
+        xc = x[:, 0] if nt == 1 else x[:, :nt].reshape(B * nt, C)
+        with _timed("proj_cls"):
+            a.proj.gemm_codes(cls_codes, p_proj, _lib.EPI_F32_RESID, out=xc)
+        codes = torch.empty((B * nt, p_fc1.kpad), dtype=torch.int8, device=x.device)
+        with _timed("ln_cls"):
+            _lib.layernorm_quant_i8(xc, self.norm2.weight, self.norm2.bias, self.norm2.eps, p_fc1.qtype,
+                                    p_fc1.d_act, p_fc1.qm_act, p_fc1.t_act, 0, codes, p_fc1.kpad,
+                                    code_table=epilogue_table(p_fc1, _lib.EPI_I8))
+        hid = torch.empty((B * nt, p_fc2.kpad), dtype=torch.int8, device=x.device)
+        if p_fc2.kpad != p_fc1.n:
+            hid[:, p_fc1.n:].zero_()
+        with _timed("fc1_cls"):
+            m.fc1.gemm_codes(codes, p_fc1, _lib.EPI_I8_GELU, out=hid, next_layer=m.fc2)
+        with _timed("fc2_cls"):
+            m.fc2.gemm_codes(hid, p_fc2, _lib.EPI_F32_RESID, out=xc)
+        return (x if nt == 1 else xc.view(B, nt, C)), None
+
+    @staticmethod
+    def _cls_rows(codes: torch.Tensor, B: int, N: int, nt: int) -> torch.Tensor:
+        """The first nt rows of every image of full-M codes [B*N, ld]: a strided view (lda = N*ld) for nt = 1."""
+        c3 = codes.view(B, N, codes.shape[1])
+        return c3[:, 0] if nt == 1 else c3[:, :nt].reshape(B * nt, codes.shape[1])
+
     def forward_fused_chain_(self, x: torch.Tensor, codes_in: Optional[torch.Tensor] = None,
-                             next_block: Optional["Block"] = None):
+                             next_block: Optional["Block"] = None, last: bool = False, num_tokens: int = 1):
         """forward_fused_ with the LayerNorms carried by the residual GEMMs: `codes_in` = this block's norm1
         codes when the previous block's fc2 produced them; with `next_block`, fc2 also produces that block's
-        norm1 codes. Returns (x, next_block's norm1 codes or None)."""
+        norm1 codes. Returns (x, next_block's norm1 codes or None).
+        `last`: this is the model's last block and only the first `num_tokens` token rows of its output are read
+        (LAST_BLOCK_CLS_ONLY): everything after the keys and values is computed for those rows only (_cls_tail_),
+        and only they are valid in the returned x ([B, N, C] for num_tokens = 1, else [B, num_tokens, C])."""
         B, N, C = x.shape
         M = B * N
         x2 = x.view(M, C)
@@ -359,10 +402,18 @@ class Block(nn.Module):
         if (a.split_ok(p_qkv) and N <= _lib.QKV_ATT_MAX_N and p_qkv.wfmt == _lib.W4 and p_qkv.kpad <= 65536
                 and p_qkv.kpad % 256 == 0 and a.num_heads * 64 <= _lib.QKV_ATT_MAX_C):
             # qkv projection + attention + proj's activation quantizer in one kernel (q/k/v stay on chip)
-            out = torch.empty((M, p_proj.kpad), dtype=torch.int8, device=x.device)
+            # (last: compact [B*nt, kpad], the wanted queries only)
+            out = torch.empty((B * num_tokens if last else M, p_proj.kpad), dtype=torch.int8, device=x.device)
             if p_proj.kpad != a.num_heads * 64:
                 out[:, a.num_heads * 64:].zero_()
             in_scale, tab = attention_in_scale(p_qkv), epilogue_table(p_proj, _lib.EPI_I8)
+            if last:
+                with _timed("qkv_attn_cls"):
+                    _lib.qkv_attention_q(codes, B, N, num_tokens, p_qkv.kpad, p_qkv.packed_codes(), p_qkv.npad,
+                                         p_qkv.d_act, p_qkv.d_wt, p_qkv.bias_pad, a.num_heads, a.scale, out,
+                                         _lib.ATT_I8, in_scale, p_proj.qtype, p_proj.d_act, p_proj.qm_act,
+                                         p_proj.t_act, epi_table=tab)
+                return self._cls_tail_(x, out, num_tokens)
             with _timed("qkv_attn"):
                 _lib.qkv_attention(codes, B, N, p_qkv.kpad, p_qkv.packed_codes(), p_qkv.npad, p_qkv.d_act, p_qkv.d_wt,
                                    p_qkv.bias_pad, a.num_heads, a.scale, out, _lib.ATT_I8, in_scale,
@@ -391,6 +442,8 @@ class Block(nn.Module):
                                  p_proj.qtype, p_proj.d_act, p_proj.qm_act, p_proj.t_act,
                                  epi_table=epilogue_table(p_proj, _lib.EPI_I8))
             trace_codes(a.proj, codes, p_proj.k)
+            if last:   # the attention in full, the rest on the class rows (lda = N * kpad)
+                return self._cls_tail_(x, self._cls_rows(codes, B, N, num_tokens), num_tokens)
             a.proj.gemm_codes(codes, p_proj, _lib.EPI_F32_RESID, out=x2)
             return self._mlp_fused_(x, x2, M, None, next_block)
         qkv = a.qkv.gemm_codes(codes, p_qkv, _lib.EPI_F32)
@@ -406,6 +459,8 @@ class Block(nn.Module):
             h = a.core(qkv, B, N).reshape(M, -1)
             codes = a.proj._act_codes(h if h.is_contiguous() else h.contiguous(), p_proj)
         trace_codes(a.proj, codes, p_proj.k)
+        if last:
+            return self._cls_tail_(x, self._cls_rows(codes, B, N, num_tokens), num_tokens)
         a.proj.gemm_codes(codes, p_proj, _lib.EPI_F32_RESID, out=x2)
         return self._mlp_fused_(x, x2, M, None, next_block)
 
@@ -559,7 +614,11 @@ class VisionTransformer(nn.Module):
             if isinstance(blk, Block) and blk.fused_ok(x):
                 nb = blocks[i + 1] if i + 1 < len(blocks) else None
                 nb = nb if isinstance(nb, Block) and nb.fused_ok(x) else None
-                x, codes = blk.forward_fused_chain_(x.contiguous(), codes, nb)
+                # the last block: only the token rows the heads read (bit-identical; off while codes are traced)
+                last = (LAST_BLOCK_CLS_ONLY and i + 1 == len(blocks) and _ql.CODE_TRACE is None
+                        and not torch.is_grad_enabled() and x.shape[1] >= self.num_tokens)
+                x, codes = blk.forward_fused_chain_(x.contiguous(), codes, nb, last=last,
+                                                    num_tokens=self.num_tokens)
             else:
                 codes = None
                 x = blk(x)

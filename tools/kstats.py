@@ -4,7 +4,9 @@
     python tools/kstats.py --split TRACE_CSV STEPS [N]   the same from a --kernel-trace kernel_trace.csv, split into
                                                         the timed steps' kernels and setup/parity kernels (needs a
                                                         bench.py run with QVIT_STEP_MARKERS=1: its two spin kernels
-                                                        bracket the timed steps)
+                                                        bracket the timed steps); with --by-grid launches of one
+                                                        kernel at different grid sizes are listed apart (the class-row
+                                                        launches of the last block beside the full-M ones)
     python tools/kstats.py --pmc FETCH_DIR WRITE_DIR [--round r01]
                                                         fc1 HBM traffic per launch from two PMC passes
 
@@ -51,7 +53,7 @@ def _table(rows, total, n, per=1):
     return out
 
 
-def split(trace, steps, n=30):
+def split(trace, steps, n=30, by_grid=False):
     """Kernels dispatched between the two marker spin kernels of bench.py (QVIT_STEP_MARKERS=1) are the timed steps'
     kernels; everything before the first / after the second marker (library build checks, calibration, epilogue
     tables, the event-timed second pass, parity/reference launches) is setup/parity."""
@@ -66,7 +68,10 @@ def split(trace, steps, n=30):
             continue
         d = step if a < i < b else other
         ns = int(r["End_Timestamp"]) - int(r["Start_Timestamp"])
-        c = d.setdefault(r["Kernel_Name"], [0, 0])
+        key = r["Kernel_Name"]
+        if by_grid and r.get("Grid_Size_X"):
+            key = f"[grid {int(r['Grid_Size_X']):>7d}] " + _short(key)
+        c = d.setdefault(key, [0, 0])
         c[0] += 1
         c[1] += ns
     span = int(rows[b]["Start_Timestamp"]) - int(rows[a]["End_Timestamp"])
@@ -154,6 +159,8 @@ if __name__ == "__main__":
         rnd = sys.argv[sys.argv.index("--round") + 1] if "--round" in sys.argv else "r01"
         pmc(sys.argv[2], sys.argv[3], rnd)
     elif sys.argv[1] == "--split":
-        split(sys.argv[2], int(sys.argv[3]), int(sys.argv[4]) if len(sys.argv) > 4 else 30)
+        by_grid = "--by-grid" in sys.argv
+        args = [a for a in sys.argv[2:] if a != "--by-grid"]
+        split(args[0], int(args[1]), int(args[2]) if len(args) > 2 else 30, by_grid)
     else:
         top(sys.argv[1], int(sys.argv[2]) if len(sys.argv) > 2 else 25)
