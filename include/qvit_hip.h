@@ -37,6 +37,10 @@
  *   qvit_ultra_*              4-bit quantization/quant_ultra.py:8-91 + mymodel.py:62-144 (UltraNet: weight
  *                             codes, BN folding, fused conv+BN+quantizer+maxpool blocks, the 26 x 26 tail of
  *                             the network in one launch, YOLO decode).
+ *   qvit_ultra_weight_quant_backward / qvit_ultra_act_quant_backward / qvit_conv_wgrad
+ *                             4-bit quantization/quant_ultra.py:8-27 (uniform_quantize's straight-through
+ *                             backward) behind :50-55 (weight_quantize_fn), :71 (activation_quantize_fn) and
+ *                             :85-89 (Conv2d_Q's F.conv2d, the weight gradient against the activation codes).
  *   qvit_attention            vit_model.py:133-149 (Attention.forward between qkv and proj):
  *                             softmax(q k^T * scale) v per (image, head), fp32 out or fused with the
  *                             proj layer's quantize_act (quant_layers.py:497) -> int8 codes.
@@ -523,6 +527,57 @@ int qvit_ultra_tail(const int8_t* in, int64_t B, int64_t H, int64_t W, const int
                     const float* hbias, int64_t hout, int w_bit, int a_bit, float* out, int64_t ldo,
                     const float* anchors, int64_t na, int64_t no, float stride, float* io, float* p,
                     hipStream_t stream);
+
+/*
+ * UltraNet training: the straight-through backward of quant_ultra.py's quantizers (uniform_quantize.backward,
+ * quant_ultra.py:23-25, hands the gradient through the rounding unchanged) and Conv2d_Q's weight gradient.
+ *
+ * qvit_ultra_weight_quant_backward: backward of weight_quantize_fn.forward, 2 <= w_bit <= 8 (quant_ultra.py:50-55:
+ *   weight = tanh(x); weight = weight / max|weight|; weight_q = uniform_q(weight)). With t = tanh(w), m = max|t|:
+ *     g_t = g / m - sgn(t) [|t| == m] (sum_i g_i t_i) / (m^2 c),   grad_w = g_t (1 - t^2),
+ *   c the number of elements attaining the maximum (torch's full-reduction max spreads its gradient evenly over
+ *   ties). t and m come from the device routines qvit_ultra_weight_codes uses, so the tie set is the forward's.
+ *   w, grad_out, grad_w : device float[n] (4-byte aligned; grad_w may be grad_out).
+ *   workspace : qvit_ultra_weight_quant_backward_workspace_bytes(n) bytes (16 + 16 per workgroup, at most 1024
+ *               workgroups), 8-byte aligned, contents irrelevant. The query returns QVIT_EINVAL for n < 0.
+ *   The sum and the count take per-thread double accumulation, a fixed-order wave / block tree, one partial per
+ *   workgroup and a one-block fold in index order: no float atomics, two calls give the same bits. Masks select: a
+ *   NaN in grad_out[i] reaches grad_w[i] and, through the sum, every tied element. n == 0 does nothing.
+ * qvit_ultra_act_quant_backward: backward of activation_quantize_fn.forward (quant_ultra.py:71,
+ *   uniform_q(clamp(x, 0, 1))): grad_x = grad_out where 0 <= x <= 1 (both boundaries pass), else 0 (a NaN x: 0).
+ *   x, grad_out, grad_x : device float[n], 16-byte aligned (QVIT_EALIGN otherwise); grad_x may be grad_out.
+ * qvit_conv_wgrad: the weight gradient of Conv2d_Q.forward's F.conv2d (quant_ultra.py:85-89) with respect to the
+ *   quantized weight, for an input that holds activation_quantize_fn values (quant_ultra.py:66-73):
+ *     dW[n][c][ky][kx] = (1 / levels) sum_{b,oy,ox} G[b][n][oy][ox] k_x[b][c][oy sh - ph + ky dh][ox sw - pw + kx dw]
+ *   G      : fp32 NCHW [B][N][OH][OW] contiguous, OH = (H + 2 ph - dh (kh - 1) - 1) / sh + 1 (OW alike).
+ *   X      : fp32 NCHW [B][C][H][W] contiguous; the caller declares X = k_x / levels with integer 0 <= k_x <= levels
+ *            (the quantizer's output, max-pooled or not). The kernel recovers k_x = rint(X levels).
+ *   levels : 1 .. 127 (2^a_bit - 1).
+ *   dW     : fp32 [N][C][kh][kw] contiguous, the layout of nn.Conv2d.weight.grad; nothing outside it is written.
+ *   workspace : qvit_conv_wgrad_workspace_bytes(...) bytes, 16-byte aligned, contents irrelevant: the reduction
+ *            range B OH OW is split over s = max(1, min(256, ceil(B OH OW / 32), ceil(2048 / tiles))) waves per
+ *            64 x 64 output tile (tiles = ceil(N / 64) ceil(C kh kw / 64)); their fp32 partials (s 64 ceil(N / 64)
+ *            64 ceil(C kh kw / 64) 4 bytes) are summed in ascending split order by a second launch. No atomics.
+ *   Zero padding, groups == 1, any stride / padding / dilation; out-of-image taps contribute zero. B == 0 writes
+ *   zeros. Sizes: C, H, W, N, strides, paddings, C kh kw <= 2^20, kh, kw, dh, dw <= 1024, OH OW <= 2^30,
+ *   B OH OW < 2^31 - 64 and a non-empty output, else QVIT_EINVAL (also from the query); pointers 4-byte aligned
+ *   (workspace 16), else QVIT_EALIGN.
+ *   fp32-GEMM accuracy, as qvit_gemm_wgrad: G is split into three bf16 terms whose sum is G exactly, every product
+ *   with a code is exact in fp32, accumulation is fp32 on v_mfma_f32_16x16x32_bf16, one multiply by 1 / levels ends
+ *   it. A NaN / inf in G[b][n][.][.] leaves dW[n] NaN and no other output channel.
+ * The input gradient needs no entry point: for stride 1 and p <= d (k - 1) it is qvit_conv_wonly with X = G, the
+ * qvit_pack_weight image of the codes transposed (C rows) and flipped in (ky, kx), and padding d (k - 1) - p.
+ */
+int64_t qvit_ultra_weight_quant_backward_workspace_bytes(int64_t n);
+int qvit_ultra_weight_quant_backward(const float* w, const float* grad_out, int64_t n, int w_bit, float* grad_w,
+                                     void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int qvit_ultra_act_quant_backward(const float* x, const float* grad_out, int64_t n, float* grad_x,
+                                  hipStream_t stream);
+int64_t qvit_conv_wgrad_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t N, int kh, int kw,
+                                        int sh, int sw, int ph, int pw, int dh, int dw);
+int qvit_conv_wgrad(const float* G, const float* X, int64_t B, int64_t C, int64_t H, int64_t W, int64_t N, int kh,
+                    int kw, int sh, int sw, int ph, int pw, int dh, int dw, int levels, float* dW, void* workspace,
+                    int64_t workspace_bytes, hipStream_t stream);
 /*
  * UltraNet integer deploy (reference `4-bit quantization/`: quantization.py:24-31,68-89,
  * qnn_param_reader.py:58-85, ultranet_param_gen.py:14-22 — the FPGA flow's integer parameters):

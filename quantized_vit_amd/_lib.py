@@ -100,6 +100,10 @@ _SIGNATURES = {
     "qvit_ultra_conv_int": [_c_p, _i64, _i64, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i32, _i32, _i32,
                             _c_p, _i64, _c_p],
     "qvit_yolo_decode": [_c_p, _i64, _i64, _i64, _i64, _i64, _i64, _c_p, _f32, _c_p, _c_p, _c_p],
+    "qvit_ultra_weight_quant_backward": [_c_p, _c_p, _i64, _i32, _c_p, _c_p, _i64, _c_p],
+    "qvit_ultra_act_quant_backward": [_c_p, _c_p, _i64, _c_p, _c_p],
+    "qvit_conv_wgrad": [_c_p, _c_p, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                        _i32, _c_p, _c_p, _i64, _c_p],
     "qvit_attention": [_c_p, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _c_p, _i64, _i32, _c_p, _c_p, _c_p,
                        _i32, _c_p],
     "qvit_gemm_qkv_split": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i64, _f32, _c_p,
@@ -120,6 +124,8 @@ INT64_FUNCS = {
     "qvit_gelu_quant_backward_workspace_bytes": [_i64],
     "qvit_attention_backward_workspace_bytes": [_i64, _i64, _i64],
     "qvit_gemm_wgrad_workspace_bytes": [_i64, _i64, _i64],
+    "qvit_ultra_weight_quant_backward_workspace_bytes": [_i64],
+    "qvit_conv_wgrad_workspace_bytes": [_i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
 }
 STRING_FUNCS = {"qvit_strerror": [_i32], "qvit_version": []}
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(INT64_FUNCS) + list(STRING_FUNCS))
@@ -904,3 +910,88 @@ def yolo_decode(head: torch.Tensor, na: int, no: int, anchors: torch.Tensor, str
     _check(load().qvit_yolo_decode(_ptr(head), B, ny, nx, na, no, C, _ptr(anchors), stride, _ptr(io), _ptr(p),
                                    _stream(head.device)), "qvit_yolo_decode")
     return io.view(B, -1, no), p
+
+
+# ---- UltraNet training (ultra_backward.hip) -----------------------------------------------------------
+def ultra_weight_quant_backward(w: torch.Tensor, grad_out: torch.Tensor, w_bit: int,
+                                grad_w: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Backward of weight_quantize_fn (2 <= w_bit <= 8) over the weight w given the gradient of its fake-quant
+    values (qvit_ultra_weight_quant_backward); shaped as w (written into `grad_w` when given; it may be grad_out)."""
+    _require_gpu(w, "weight")
+    _require_gpu(grad_out, "grad_out")
+    wc = w.detach().contiguous().float()
+    gc = grad_out.detach().contiguous().float()
+    if wc.numel() != gc.numel():
+        raise QvitError(f"ultra_weight_quant_backward: grad_out has {gc.numel()} elements for {wc.numel()} weights")
+    if grad_w is None:
+        grad_w = torch.empty_like(wc)
+    assert grad_w.is_cuda and grad_w.dtype == torch.float32 and grad_w.is_contiguous() and \
+        grad_w.numel() == wc.numel()
+    n = wc.numel()
+    lib = load()
+    nbytes = int(lib.qvit_ultra_weight_quant_backward_workspace_bytes(n))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=wc.device)
+    _check(lib.qvit_ultra_weight_quant_backward(_ptr(wc), _ptr(gc), n, w_bit, _ptr(grad_w), _ptr(ws), nbytes,
+                                                _stream(wc.device)), "qvit_ultra_weight_quant_backward")
+    return grad_w
+
+
+def ultra_act_quant_backward(x: torch.Tensor, grad_out: torch.Tensor,
+                             grad_x: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Backward of activation_quantize_fn over its input x: grad_out where 0 <= x <= 1, else 0
+    (qvit_ultra_act_quant_backward); shaped as x (written into `grad_x` when given; it may be grad_out)."""
+    _require_gpu(x, "input")
+    _require_gpu(grad_out, "grad_out")
+    xc = x.detach().contiguous().float()
+    gc = grad_out.detach().contiguous().float()
+    if xc.numel() != gc.numel():
+        raise QvitError(f"ultra_act_quant_backward: grad_out has {gc.numel()} elements for an input of {xc.numel()}")
+    if xc.data_ptr() % 16:
+        xc = xc.clone()
+    if gc.data_ptr() % 16:
+        gc = gc.clone()
+    if grad_x is None:
+        grad_x = torch.empty_like(xc)
+    assert grad_x.is_cuda and grad_x.dtype == torch.float32 and grad_x.is_contiguous() and \
+        grad_x.numel() == xc.numel()
+    if xc.numel():
+        _check(load().qvit_ultra_act_quant_backward(_ptr(xc), _ptr(gc), xc.numel(), _ptr(grad_x),
+                                                    _stream(xc.device)), "qvit_ultra_act_quant_backward")
+    return grad_x
+
+
+def conv_wgrad(G: torch.Tensor, x: torch.Tensor, kernel_size, stride, padding, dilation, levels: int,
+               out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Weight gradient [N, C, kh, kw] of F.conv2d(x, w) (groups 1, zero padding) given the output's gradient G
+    [B, N, OH, OW], for an x that holds k / levels with integer 0 <= k <= levels (activation_quantize_fn's output):
+    qvit_conv_wgrad, an implicit GEMM of G against the integer codes. `out`: a contiguous fp32 [N, C, kh, kw];
+    `workspace`: float32, at least the query's bytes (contents irrelevant)."""
+    _require_gpu(G, "grad_out")
+    _require_gpu(x, "input")
+    assert G.dim() == 4 and x.dim() == 4 and G.shape[0] == x.shape[0]
+    if G.dtype != torch.float32 or not G.is_contiguous():
+        G = G.float().contiguous()
+    if x.dtype != torch.float32 or not x.is_contiguous():
+        x = x.float().contiguous()
+    B, C, H, W = x.shape
+    N = G.shape[1]
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = kernel_size, stride, padding, dilation
+    OH = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
+    OW = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    if tuple(G.shape) != (B, N, OH, OW):
+        raise QvitError(f"conv_wgrad: grad_out {tuple(G.shape)} for an output of {(B, N, OH, OW)}")
+    if out is None:
+        out = torch.empty((N, C, kh, kw), dtype=torch.float32, device=G.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (N, C, kh, kw)
+    if B == 0:   # (an empty tensor has no device pointer to hand over)
+        return out.zero_()
+    lib = load()
+    nbytes = int(lib.qvit_conv_wgrad_workspace_bytes(B, C, H, W, N, kh, kw, sh, sw, ph, pw, dh, dw))
+    if nbytes < 0:
+        _check(nbytes, "qvit_conv_wgrad_workspace_bytes")
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=G.device)
+    _check(lib.qvit_conv_wgrad(_ptr(G), _ptr(x), B, C, H, W, N, kh, kw, sh, sw, ph, pw, dh, dw, int(levels),
+                               _ptr(out), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                               _stream(G.device)), "qvit_conv_wgrad")
+    return out

@@ -26,20 +26,13 @@
 //                               (+ pool) -> NHWC codes, or (head) acc/105 + bias -> fp32 NHWC.
 //   yolo_decode               : YOLOLayer eval decode (mymodel.py:47-60) from the head's NHWC output.
 #include "qvit_common.h"
+#include "ultra_quant_common.h"
 
 namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 
-// ---- weight quantizer ----------------------------------------------------------------------------
-__global__ void ultra_wmax_kernel(const float* __restrict__ w, int64_t n, unsigned* __restrict__ maxbits) {
-  float m = 0.f;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    m = fmaxf(m, fabsf(tanhf(w[i])));
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) atomicMax(maxbits, __float_as_uint(m));  // m >= 0: bit order == value order
-}
-
+// ---- weight quantizer (ultra_wmax_kernel: ultra_quant_common.h, shared with the backward) ---------
 // codes[o][k], k = (ky * ks + kx) * cin + c, rows >= cout and columns >= ks*ks*cin zero
 __global__ void ultra_wcodes_kernel(const float* __restrict__ w, int cout, int cin, int ks,
                                     const unsigned* __restrict__ maxbits, float n, int8_t* __restrict__ codes,
@@ -52,7 +45,7 @@ __global__ void ultra_wcodes_kernel(const float* __restrict__ w, int cout, int c
     if (o < cout && k < ks * ks * cin) {
       const int tap = k / cin, c = k % cin;
       const int64_t src = (((int64_t)o * cin + c) * ks + tap / ks) * ks + tap % ks;
-      const float t = tanhf(w[src]);
+      const float t = ultra_tanh(w[src]);
       const float kq = rintf((t / m) * n);  // quant_ultra.py:52-55 + :20: round((tanh(w)/max) * n)
       code = (int8_t)kq;
       if (values) values[src] = kq / n;     // the reference's value round(.) / n, original layout

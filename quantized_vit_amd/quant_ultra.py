@@ -16,10 +16,20 @@ packed once per weight version. w_bit 32 (no quantization: a plain conv / linear
 k = 0 quantizer divides by zero) keep the library call on the device, as do grouped or non-zero-padded convs.
 
 The network-level fused path (conv + BN + quantizer + max pool on codes) is in ultranet.py; these
-modules are the per-layer surface. Forward-only (inference): the reference's straight-through
-backward is not provided.
+modules are the per-layer surface.
+
+Training: under autograd every quantizer carries the reference's straight-through backward
+(uniform_quantize.backward, quant_ultra.py:23-25). The forward stays the no_grad HIP call, bit for bit, with one
+autograd node around it; the node's backward runs qvit_ultra_weight_quant_backward (tanh and max|.| behind the
+straight-through rounding), qvit_ultra_act_quant_backward (the clamp mask), and for Conv2d_Q / Linear_Q the input
+gradient as qvit_conv_wonly / qvit_gemm_wonly on the transposed (and, for a conv, flipped) codes and the weight
+gradient as qvit_conv_wgrad when the caller states that the input holds activation codes (`in_levels`).
+QVIT_ULTRA_BWD=hip|torch|dgrad|wgrad selects which of the two contractions run on these kernels (torch: both on
+the library; the quantizer backwards stay in HIP).
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -33,18 +43,86 @@ def _check_gpu(x: torch.Tensor, what: str) -> None:
         raise _lib.QvitError(f"{what} on {x.device}: the UltraNet path runs on a ROCm device (no CPU fallback)")
 
 
-def uniform_quantize(k):
-    """quant_ultra.py:8-27. Returns the quantizer function (the reference returns an autograd apply)."""
+# The two contractions behind Conv2d_Q / Linear_Q's backward: "hip" runs the input gradient (dgrad) on
+# qvit_conv_wonly / qvit_gemm_wonly and a conv's weight gradient (wgrad) on qvit_conv_wgrad; "torch" keeps both on
+# the library (torch.nn.grad / torch.mm); "dgrad" / "wgrad" select one op. The quantizer backwards are HIP on every
+# setting. Measured at 416 x 416 b64 only (profiles/ultra_train_bench.txt): qvit_conv_wgrad
+# is slower than the library at every UltraNet layer shape, and the input gradient on qvit_conv_wonly is slower on
+# maps of 104 x 104 and more, faster from 52 x 52 down. So under "hip" the ops named in ULTRA_BWD_DEFAULT_TORCH stay
+# on the library and dgrad runs on HIP only where the conv's input (the gradient it produces) has at most
+# DGRAD_HIP_MAX_PIXELS pixels per image: a cutoff between the two measured sizes, not measured at other batch
+# sizes. Naming an op ("dgrad" / "wgrad") runs it on HIP at every shape.
+ULTRA_BWD = os.environ.get("QVIT_ULTRA_BWD", "hip")
+ULTRA_BWD_DEFAULT_TORCH = ("wgrad",)
+DGRAD_HIP_MAX_PIXELS = 64 * 64
+_ULTRA_BWD_OPS = {"hip": ("dgrad", "wgrad"), "torch": (), "dgrad": ("dgrad",), "wgrad": ("wgrad",)}
+if ULTRA_BWD not in _ULTRA_BWD_OPS:
+    raise ValueError(f"QVIT_ULTRA_BWD={ULTRA_BWD!r}: expected hip, torch, dgrad or wgrad")
 
-    def qfn(x: torch.Tensor) -> torch.Tensor:
+
+def _backward_gemm_ops() -> tuple:
+    try:
+        ops = _ULTRA_BWD_OPS[ULTRA_BWD]
+    except KeyError:
+        raise ValueError(f"ULTRA_BWD = {ULTRA_BWD!r}: expected hip, torch, dgrad or wgrad") from None
+    return tuple(o for o in ops if o not in ULTRA_BWD_DEFAULT_TORCH) if ULTRA_BWD == "hip" else ops
+
+
+class _UniformSTE(torch.autograd.Function):
+    """quant_ultra.py:11-27: the k-bit uniform quantizer with the straight-through backward."""
+
+    @staticmethod
+    def forward(ctx, x, k):
         if k == 32:
-            return x
+            return x.view_as(x)
         if k == 1:
             return torch.sign(x)
         n = float(2 ** k - 1)
         return torch.round(x * n) / n
 
+    @staticmethod
+    def backward(ctx, grad_output):
+        return grad_output.clone(), None   # :24-25
+
+
+def uniform_quantize(k):
+    """quant_ultra.py:8-27. Returns the quantizer function, an autograd apply as the reference's."""
+
+    def qfn(x: torch.Tensor) -> torch.Tensor:
+        return _UniformSTE.apply(x, k)
+
     return qfn
+
+
+class _WeightQuantSTE(torch.autograd.Function):
+    """weight_quantize_fn.forward for 2 <= w_bit <= 8 (quant_ultra.py:50-55) as one node: the HIP quantizer's
+    values forward, qvit_ultra_weight_quant_backward backward."""
+
+    @staticmethod
+    def forward(ctx, x, w_bit):
+        ctx.save_for_backward(x)
+        ctx.w_bit = w_bit
+        return _weight_values(x, w_bit)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (x,) = ctx.saved_tensors
+        return _lib.ultra_weight_quant_backward(x, grad_output, ctx.w_bit).reshape(x.shape).to(x.dtype), None
+
+
+class _ActQuantSTE(torch.autograd.Function):
+    """activation_quantize_fn.forward for a_bit <= 7 (quant_ultra.py:71) as one node: the HIP quantizer forward,
+    the clamp mask (qvit_ultra_act_quant_backward) backward."""
+
+    @staticmethod
+    def forward(ctx, x, levels):
+        ctx.save_for_backward(x)
+        return _lib.fake_quant_f32(x, _lib.QT_ULTRA_ACT, None, None, None, levels).reshape(x.shape)
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        (x,) = ctx.saved_tensors
+        return _lib.ultra_act_quant_backward(x, grad_output).reshape(x.shape).to(x.dtype), None
 
 
 def _round_up(v: int, m: int) -> int:
@@ -59,6 +137,14 @@ def weight_codes(weight: torch.Tensor, w_bit: int, kpad: int = None, cout_pad: i
     kpad = kpad or _round_up(ks * ks * cin, 16)
     cout_pad = cout_pad or cout
     return _lib.ultra_weight_codes(w4, w_bit, kpad, cout_pad)
+
+
+def _weight_values(x: torch.Tensor, w_bit: int) -> torch.Tensor:
+    """The fake-quant weight round(.) / n (:20) of the HIP quantizer, divided on the device as IEEE fp32."""
+    w4 = x if x.dim() == 4 else x.reshape(x.shape[0], -1, 1, 1)
+    cout, cin, ks, _ = w4.shape
+    _, vals = _lib.ultra_weight_codes(w4, w_bit, _round_up(ks * ks * cin, 16), cout, values=True)
+    return vals.reshape(x.shape)
 
 
 class weight_quantize_fn(nn.Module):
@@ -77,10 +163,9 @@ class weight_quantize_fn(nn.Module):
             E = torch.mean(torch.abs(x)).detach()
             return (self.uniform_q(x / E) + 1) / 2 * E
         _check_gpu(x, "weight")
-        w4 = x if x.dim() == 4 else x.reshape(x.shape[0], -1, 1, 1)
-        cout, cin, ks, _ = w4.shape
-        _, vals = _lib.ultra_weight_codes(w4, self.w_bit, _round_up(ks * ks * cin, 16), cout, values=True)
-        return vals.reshape(x.shape)   # round(.)/n (:20), divided on the device as IEEE fp32
+        if torch.is_grad_enabled() and x.requires_grad:
+            return _WeightQuantSTE.apply(x, self.w_bit)
+        return _weight_values(x, self.w_bit)
 
 
 class activation_quantize_fn(nn.Module):
@@ -98,6 +183,8 @@ class activation_quantize_fn(nn.Module):
         _check_gpu(x, "activation")
         if self.a_bit > 7:   # levels beyond the int8 code range: the reference arithmetic on the device
             return self.uniform_q(torch.clamp(x, 0, 1))
+        if torch.is_grad_enabled() and x.requires_grad:
+            return _ActQuantSTE.apply(x, 2 ** self.a_bit - 1)
         return _lib.fake_quant_f32(x, _lib.QT_ULTRA_ACT, None, None, None, 2 ** self.a_bit - 1).reshape(x.shape)
 
 
@@ -128,8 +215,28 @@ class _PackedCodes:
                                        torch.full((1,), 1024.0, device=dev), None, self.wfmt, self.npad, self.kpad, ovf)
         self.d_wt = torch.full((1,), 1.0 / n_lvl, dtype=torch.float32, device=dev)
         self.bias_pad = _lib.pad_bias(bias, cout, self.npad, dev)
+        self._shape4, self._w_bit, self._packed_t = (cout, cin, kh, kw), w_bit, None
         self.key = key
         return self
+
+    def packed_t(self, weight: torch.Tensor):
+        """(image, rows, npad, kpad) of the codes for the input gradient: transposed (rows = input channels,
+        reduction = (output channel, ky, kx)) and flipped in (ky, kx), one qvit_pack_weight call in the forward's
+        wfmt. Built from `weight` (the tensor get() was last called with) on the first backward that needs it and
+        kept until the weight changes (get() drops it); nothing is held for it before that."""
+        if self._packed_t is None:
+            cout, cin, kh, kw = self._shape4
+            k = cin * kh * kw
+            codes = _lib.ultra_weight_codes(weight.detach().reshape(cout, cin, kh, kw), self._w_bit,
+                                            _round_up(k, 16), cout)       # (ky, kx, c) order, as get()
+            ct = codes[:, :k].view(cout, kh, kw, cin).float().flip(1, 2).permute(3, 0, 1, 2).reshape(cin, cout * kh * kw)
+            npad_t, kpad_t = _round_up(cin, _lib.TILE_N), _round_up(cout * kh * kw, _lib.TILE_K)
+            dev = ct.device
+            ovf = torch.zeros(1, dtype=torch.int32, device=dev)
+            img = _lib.pack_weight(ct.contiguous(), _lib.QT_LINEAR, torch.ones(1, device=dev),
+                                   torch.full((1,), 1024.0, device=dev), None, self.wfmt, npad_t, kpad_t, ovf)
+            self._packed_t = (img, cin, npad_t, kpad_t)
+        return self._packed_t
 
 
 def _codes_path(w_bit: int) -> bool:
@@ -137,9 +244,121 @@ def _codes_path(w_bit: int) -> bool:
 
 
 def _needs_grad(module: nn.Module, input: torch.Tensor) -> bool:
-    """Autograd wants this call's history: the packed-codes kernels record none, so such calls take the
-    reference's own F.conv2d / F.linear on quantize_fn(weight) (quant_ultra.py:85-89, :219-222), gradients included."""
+    """Autograd wants this call's history: the packed-codes kernels record none, so such calls go
+    through one autograd node around the same kernel (_ConvQFunction / _LinearQFunction)."""
     return torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
+def _conv_codes_forward(module, input: torch.Tensor) -> torch.Tensor:
+    c = module._codes.get(module.weight, module.bias, module.w_bit)
+    return _lib.conv_wonly(input.detach(), module.kernel_size, module.stride, module.padding, module.dilation,
+                           c.packed, c.wfmt, c.n, c.npad, c.kpad, c.d_wt, c.bias_pad)
+
+
+class _ConvQFunction(torch.autograd.Function):
+    """Conv2d_Q.forward on the codes path (quant_ultra.py:85-89) as one node: forward the qvit_conv_wonly call the
+    module makes under no_grad; backward grad_bias = sum G, the input gradient on qvit_conv_wonly with the
+    transposed and flipped codes (stride 1 and p <= d (k - 1); else torch.nn.grad.conv2d_input), the quantized
+    weight's gradient on qvit_conv_wgrad (input declared as k / in_levels; else torch.nn.grad.conv2d_weight), and
+    qvit_ultra_weight_quant_backward on it. Each only when its gradient is needed."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, module, in_levels):
+        ctx.module, ctx.in_levels = module, in_levels
+        ctx.save_for_backward(input, weight)
+        return _conv_codes_forward(module, input)
+
+    @staticmethod
+    def backward(ctx, G):
+        input, weight = ctx.saved_tensors
+        mod = ctx.module
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        ops = _backward_gemm_ops()
+        G = G.detach().float().contiguous()
+        ks, st, pd, dl = mod.kernel_size, mod.stride, mod.padding, mod.dilation
+        grad_x = grad_w = grad_b = None
+        if need_b:
+            grad_b = G.sum((0, 2, 3)).to(mod.bias.dtype)
+        if need_x:
+            pad_t = tuple(d * (k - 1) - p for d, k, p in zip(dl, ks, pd))
+            small = ULTRA_BWD != "hip" or input.shape[2] * input.shape[3] <= DGRAD_HIP_MAX_PIXELS
+            if "dgrad" in ops and small and st == (1, 1) and min(pad_t) >= 0:
+                c = mod._codes.get(weight, mod.bias, mod.w_bit)
+                img, rows, npad_t, kpad_t = c.packed_t(weight)
+                grad_x = _lib.conv_wonly(G, ks, st, pad_t, dl, img, c.wfmt, rows, npad_t, kpad_t, c.d_wt, None)
+            else:
+                with torch.no_grad():
+                    grad_x = torch.nn.grad.conv2d_input(input.shape, _weight_values(weight, mod.w_bit), G, st, pd,
+                                                        dl, 1)
+            grad_x = grad_x.to(input.dtype)
+        if need_w:
+            xd = input.detach()
+            if "wgrad" in ops and ctx.in_levels:
+                grad_wq = _lib.conv_wgrad(G, xd, ks, st, pd, dl, ctx.in_levels)
+            else:
+                with torch.no_grad():
+                    grad_wq = torch.nn.grad.conv2d_weight(xd.float(), weight.shape, G, st, pd, dl, 1)
+            grad_w = _lib.ultra_weight_quant_backward(weight, grad_wq, mod.w_bit).reshape(weight.shape).to(
+                weight.dtype)
+        return grad_x, grad_w, grad_b, None, None
+
+
+def _linear_codes_forward(module, input: torch.Tensor) -> torch.Tensor:
+    c = module._codes.get(module.weight, module.bias, module.w_bit)
+    x2 = input.detach().reshape(-1, module.in_features)
+    if (x2.dtype != torch.float32 or x2.stride(-1) != 1 or c.kpad != module.in_features or x2.stride(0) % 4
+            or x2.data_ptr() % 16):
+        xp = torch.zeros((x2.shape[0], c.kpad), dtype=torch.float32, device=x2.device)
+        xp[:, :module.in_features] = x2
+        x2 = xp
+    ldy = _round_up(c.n, 4)
+    y = torch.empty((x2.shape[0], ldy), dtype=torch.float32, device=x2.device)
+    _lib.gemm_wonly(x2, x2.shape[0], c.kpad, c.packed, c.wfmt, c.n, c.npad, c.d_wt, c.bias_pad, y)
+    y = y if ldy == c.n else y[:, :c.n]
+    return y.reshape(*input.shape[:-1], c.n)
+
+
+class _LinearQFunction(torch.autograd.Function):
+    """Linear_Q.forward on the codes path (quant_ultra.py:219-222) as one node: forward the qvit_gemm_wonly call;
+    backward the input gradient on qvit_gemm_wonly with the transposed codes (as QuantizeLinear's), the quantized
+    weight's gradient on torch.mm (the input is fp32) and qvit_ultra_weight_quant_backward on it."""
+
+    @staticmethod
+    def forward(ctx, input, weight, bias, module):
+        ctx.module = module
+        ctx.save_for_backward(input, weight)
+        return _linear_codes_forward(module, input)
+
+    @staticmethod
+    def backward(ctx, G):
+        input, weight = ctx.saved_tensors
+        mod = ctx.module
+        need_x, need_w, need_b = ctx.needs_input_grad[:3]
+        G2 = G.detach().float().reshape(-1, mod.out_features).contiguous()
+        M = G2.shape[0]
+        grad_x = grad_w = grad_b = None
+        if need_b:
+            grad_b = G2.sum(0).to(mod.bias.dtype)
+        if need_x:
+            if "dgrad" in _backward_gemm_ops() and M:
+                c = mod._codes.get(weight, mod.bias, mod.w_bit)
+                img, rows, npad_t, kpad_t = c.packed_t(weight)
+                Gp = G2
+                if G2.shape[1] != kpad_t or G2.data_ptr() % 16:
+                    Gp = torch.zeros((M, kpad_t), dtype=torch.float32, device=G2.device)
+                    Gp[:, :mod.out_features] = G2
+                ldy = _round_up(rows, 4)
+                y = torch.empty((M, ldy), dtype=torch.float32, device=G2.device)
+                _lib.gemm_wonly(Gp, M, kpad_t, img, c.wfmt, rows, npad_t, c.d_wt, None, y)
+                gx2 = y if ldy == rows else y[:, :rows]
+            else:
+                gx2 = torch.mm(G2, _weight_values(weight, mod.w_bit))
+            grad_x = gx2.reshape(input.shape).to(input.dtype)
+        if need_w:
+            grad_wq = torch.mm(G2.t(), input.detach().reshape(-1, mod.in_features).float())
+            grad_w = _lib.ultra_weight_quant_backward(weight, grad_wq, mod.w_bit).reshape(weight.shape).to(
+                weight.dtype)
+        return grad_x, grad_w, grad_b, None
 
 
 def conv2d_Q_fn(w_bit):
@@ -168,14 +387,17 @@ def conv2d_Q_fn(w_bit):
             self._bn_fold = None
             return self
 
-        def forward(self, input, order=None):
+        def forward(self, input, order=None, _in_levels=None):
+            """`_in_levels` (private; UltraNetQua.forward_modules passes it): the caller's statement that `input`
+            holds k / _in_levels with integer 0 <= k <= _in_levels, the output of an activation_quantize_fn
+            (max-pooled or not), which puts the weight gradient on qvit_conv_wgrad."""
             if _codes_path(self.w_bit):
                 _check_gpu(input, "input")
             if _codes_path(self.w_bit) and self.groups == 1 and self.padding_mode == "zeros" and \
-                    not isinstance(self.padding, str) and input.dim() == 4 and not _needs_grad(self, input):
-                c = self._codes.get(self.weight, self.bias, self.w_bit)
-                return _lib.conv_wonly(input.detach(), self.kernel_size, self.stride, self.padding, self.dilation,
-                                       c.packed, c.wfmt, c.n, c.npad, c.kpad, c.d_wt, c.bias_pad)
+                    not isinstance(self.padding, str) and input.dim() == 4:
+                if _needs_grad(self, input):
+                    return _ConvQFunction.apply(input, self.weight, self.bias, self, _in_levels)
+                return _conv_codes_forward(self, input)
             weight_q = self.quantize_fn(self.weight)
             return F.conv2d(input, weight_q, self.bias, self.stride, self.padding, self.dilation, self.groups)
 
@@ -271,20 +493,11 @@ def linear_Q_fn(w_bit):
             return self
 
         def forward(self, input):
-            if not _codes_path(self.w_bit) or _needs_grad(self, input):
+            if not _codes_path(self.w_bit):
                 return F.linear(input, self.quantize_fn(self.weight), self.bias)
             _check_gpu(input, "input")
-            c = self._codes.get(self.weight, self.bias, self.w_bit)
-            x2 = input.detach().reshape(-1, self.in_features)
-            if (x2.dtype != torch.float32 or x2.stride(-1) != 1 or c.kpad != self.in_features or x2.stride(0) % 4
-                    or x2.data_ptr() % 16):
-                xp = torch.zeros((x2.shape[0], c.kpad), dtype=torch.float32, device=x2.device)
-                xp[:, :self.in_features] = x2
-                x2 = xp
-            ldy = _round_up(c.n, 4)
-            y = torch.empty((x2.shape[0], ldy), dtype=torch.float32, device=x2.device)
-            _lib.gemm_wonly(x2, x2.shape[0], c.kpad, c.packed, c.wfmt, c.n, c.npad, c.d_wt, c.bias_pad, y)
-            y = y if ldy == c.n else y[:, :c.n]
-            return y.reshape(*input.shape[:-1], c.n)
+            if _needs_grad(self, input):
+                return _LinearQFunction.apply(input, self.weight, self.bias, self)
+            return _linear_codes_forward(self, input)
 
     return Linear_Q

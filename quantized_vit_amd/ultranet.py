@@ -221,20 +221,32 @@ class UltraNetQua(nn.Module):
         inside the 1e-3 end-to-end bar) unless one of the three modules carries forward (pre-)hooks or global module
         hooks are registered, which then run module by module as usual; the Sequential's own forward hooks are not
         called on this walk. Any image size, training mode included; under autograd (grad mode on and a
-        parameter or the input requiring grad) the Conv2d_Q layers take the reference's F.conv2d on the fake-quant
-        weight instead, so gradients flow (the packed-codes kernels record no history)."""
+        parameter or the input requiring grad) every Conv2d_Q and quantizer records one node around the same HIP
+        forward, with the reference's straight-through backward (quant_ultra.py). This walk
+        knows what feeds each conv: an activation_quantize_fn with a_bit <= 7, max-pooled or not, leaves values
+        k / (2^a_bit - 1), and the conv is told so (`_in_levels`), which puts its weight gradient on
+        qvit_conv_wgrad; BatchNorm2d and MaxPool2d train on ATen."""
         img_size = x.shape[-2:]
         yolo_out = []
         with _aten_batch_norm():
             mods, i = list(self.layers), 0
+            levels = None   # the input holds k / levels (what the module before this one wrote), if known
             while i < len(mods):
                 m = mods[i]
                 if hasattr(m, "forward_bn_act") and i + 2 < len(mods) and not _hooked(mods[i:i + 3]):
                     y = m.forward_bn_act(x, mods[i + 1], mods[i + 2])   # conv -> BN -> quantizer in one launch
                     if y is not None:
-                        x, i = y, i + 3
+                        x, i, levels = y, i + 3, 2 ** mods[i + 2].a_bit - 1
                         continue
-                x, i = m(x), i + 1
+                if levels is not None and hasattr(m, "forward_bn_act") and torch.is_grad_enabled():
+                    x = m(x, _in_levels=levels)   # (through __call__: every hook of the module still runs)
+                else:
+                    x = m(x)
+                if isinstance(m, activation_quantize_fn) and m.a_bit <= 7:
+                    levels = 2 ** m.a_bit - 1
+                elif not isinstance(m, nn.MaxPool2d):
+                    levels = None
+                i += 1
         x = self.yololayer(x, img_size)
         yolo_out.append(x)
         if self.training:
