@@ -41,6 +41,10 @@
  *                             4-bit quantization/quant_ultra.py:8-27 (uniform_quantize's straight-through
  *                             backward) behind :50-55 (weight_quantize_fn), :71 (activation_quantize_fn) and
  *                             :85-89 (Conv2d_Q's F.conv2d, the weight gradient against the activation codes).
+ *   qvit_bn_stats / qvit_bn_act_pool_forward / qvit_bn_act_pool_backward_reduce / qvit_bn_act_pool_backward_dx
+ *                             4-bit quantization/mymodel.py:71-124 in training mode: the nn.BatchNorm2d (batch
+ *                             statistics) -> activation_quantize_fn (quant_ultra.py:59-73) -> nn.MaxPool2d(2, 2)
+ *                             run between two Conv2d_Q, forward and backward, as streaming passes over NCHW fp32.
  *   qvit_attention            vit_model.py:133-149 (Attention.forward between qkv and proj):
  *                             softmax(q k^T * scale) v per (image, head), fp32 out or fused with the
  *                             proj layer's quantize_act (quant_layers.py:497) -> int8 codes.
@@ -578,6 +582,51 @@ int64_t qvit_conv_wgrad_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t
 int qvit_conv_wgrad(const float* G, const float* X, int64_t B, int64_t C, int64_t H, int64_t W, int64_t N, int kh,
                     int kw, int sh, int sw, int ph, int pw, int dh, int dw, int levels, float* dW, void* workspace,
                     int64_t workspace_bytes, hipStream_t stream);
+/*
+ * UltraNet training: BatchNorm2d on batch statistics -> activation_quantize_fn (a_bit <= 7) -> optional
+ * MaxPool2d(2, 2) (mymodel.py:71-124) over x fp32 NCHW [B][C][H][W] contiguous, M = B H W values per channel.
+ * Common to the entry points below: B, C, H, W >= 1 and each < 2^31, H W <= 2^31 - 1 - 8192, B C < 2^31,
+ * M >= 2, pool 0 or 1 and then H, W >= 2, and B C ceil(H W / 8192) < 2^31 (the grid), else QVIT_EINVAL (also from
+ * the workspace queries); fp32 pointers 4-byte aligned, sums and workspaces 8, else QVIT_EALIGN. The 16-byte arm
+ * runs when the tensors are 16-byte aligned (flag bytes: 4) and H W % 4 == 0 (pooled: W % 4 == 0), else a scalar
+ * arm with the same results. Reductions: double accumulation per thread, a fixed-order wave / workgroup tree, one
+ * partial pair per workgroup in the workspace (contents irrelevant), folded per channel in index order. No atomics:
+ * two calls give the same bits.
+ *
+ * qvit_bn_stats: mean[c], var[c] (biased) and invstd[c] = 1 / sqrt(var + eps) (computed in double on data shifted
+ *   by x[0][c][0][0], rounded once to fp32), and when the running pointers are not NULL nn.BatchNorm2d's update
+ *   r = (1 - factor) r + factor new with new = mean, resp. var M / (M - 1); factor is the module's momentum or
+ *   1 / num_batches_tracked. workspace: qvit_bn_stats_workspace_bytes(B, C, H, W) = 16 B C ceil(H W / 8192) bytes.
+ * qvit_bn_act_pool_forward: a = gamma[c] invstd[c] (fp32; gamma NULL: 1), y = fmaf(x - mean[c], a, beta[c]) (beta
+ *   NULL: 0), k = rint(clamp(y, 0, 1) levels) (a NaN y: 0), pass = 0 <= y <= 1 (both edges pass, a NaN fails: the
+ *   mask of qvit_ultra_act_quant_backward). levels 1 .. 127.
+ *   pool 0: out [B][C][H][W] = k / levels, flags [B][C][H][W] bytes = pass.
+ *   pool 1: 2 x 2 windows, stride 2, floor mode (an odd last row / column is dropped): out [B][C][H/2][W/2] = the
+ *     window's maximum k / levels; flags [B][C][H/2][W/2] = pass(winner) | winner << 1 with winner = 2 dy + dx of the
+ *     FIRST maximum in row-major order (ATen's max pool: val > maxval), so equal codes select the top-left element.
+ * qvit_bn_act_pool_backward_reduce: g_y = grad_out (shaped as out) at the element / the window's winner when its
+ *   pass bit is set, else 0 (selected, never multiplied: a NaN grad_out behind a cleared bit is not read into a
+ *   sum); sums[c] = S1 = sum g_y, sums[C + c] = S2 = sum g_y xhat, xhat = (x - mean) invstd. sums: double[2 C].
+ *   workspace: qvit_bn_act_pool_backward_workspace_bytes(B, C, H, W, pool) bytes.
+ * qvit_bn_act_pool_backward_dx: dx [B][C][H][W] = a (g_y - S1 / M - xhat S2 / M) at every element of x (pooled-away
+ *   elements and dropped rows / columns have g_y = 0), dgamma[c] = S2 and dbeta[c] = S1 when those are not NULL.
+ */
+int64_t qvit_bn_stats_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W);
+int qvit_bn_stats(const float* x, int64_t B, int64_t C, int64_t H, int64_t W, double eps, double factor,
+                  float* running_mean, float* running_var, float* mean, float* var, float* invstd, void* workspace,
+                  int64_t workspace_bytes, hipStream_t stream);
+int qvit_bn_act_pool_forward(const float* x, int64_t B, int64_t C, int64_t H, int64_t W, const float* mean,
+                             const float* invstd, const float* gamma, const float* beta, int levels, int pool,
+                             float* out, uint8_t* flags, hipStream_t stream);
+int64_t qvit_bn_act_pool_backward_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int pool);
+int qvit_bn_act_pool_backward_reduce(const float* x, const float* grad_out, const uint8_t* flags, int64_t B,
+                                     int64_t C, int64_t H, int64_t W, const float* mean, const float* invstd,
+                                     int pool, double* sums, void* workspace, int64_t workspace_bytes,
+                                     hipStream_t stream);
+int qvit_bn_act_pool_backward_dx(const float* x, const float* grad_out, const uint8_t* flags, int64_t B, int64_t C,
+                                 int64_t H, int64_t W, const float* mean, const float* invstd, const float* gamma,
+                                 const double* sums, int pool, float* dx, float* dgamma, float* dbeta,
+                                 hipStream_t stream);
 /*
  * UltraNet integer deploy (reference `4-bit quantization/`: quantization.py:24-31,68-89,
  * qnn_param_reader.py:58-85, ultranet_param_gen.py:14-22 — the FPGA flow's integer parameters):

@@ -53,6 +53,7 @@ _c_p = ctypes.c_void_p
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int
 _f32 = ctypes.c_float
+_f64 = ctypes.c_double
 
 # name -> argtypes (restype is int for all but the string getters)
 _SIGNATURES = {
@@ -104,6 +105,12 @@ _SIGNATURES = {
     "qvit_ultra_act_quant_backward": [_c_p, _c_p, _i64, _c_p, _c_p],
     "qvit_conv_wgrad": [_c_p, _c_p, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                         _i32, _c_p, _c_p, _i64, _c_p],
+    "qvit_bn_stats": [_c_p, _i64, _i64, _i64, _i64, _f64, _f64, _c_p, _c_p, _c_p, _c_p, _c_p, _c_p, _i64, _c_p],
+    "qvit_bn_act_pool_forward": [_c_p, _i64, _i64, _i64, _i64, _c_p, _c_p, _c_p, _c_p, _i32, _i32, _c_p, _c_p, _c_p],
+    "qvit_bn_act_pool_backward_reduce": [_c_p, _c_p, _c_p, _i64, _i64, _i64, _i64, _c_p, _c_p, _i32, _c_p, _c_p, _i64,
+                                         _c_p],
+    "qvit_bn_act_pool_backward_dx": [_c_p, _c_p, _c_p, _i64, _i64, _i64, _i64, _c_p, _c_p, _c_p, _c_p, _i32, _c_p,
+                                     _c_p, _c_p, _c_p],
     "qvit_attention": [_c_p, _i64, _i64, _i64, _i64, _i64, _f32, _f32, _i32, _c_p, _i64, _i32, _c_p, _c_p, _c_p,
                        _i32, _c_p],
     "qvit_gemm_qkv_split": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i64, _f32, _c_p,
@@ -126,6 +133,8 @@ INT64_FUNCS = {
     "qvit_gemm_wgrad_workspace_bytes": [_i64, _i64, _i64],
     "qvit_ultra_weight_quant_backward_workspace_bytes": [_i64],
     "qvit_conv_wgrad_workspace_bytes": [_i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
+    "qvit_bn_stats_workspace_bytes": [_i64, _i64, _i64, _i64],
+    "qvit_bn_act_pool_backward_workspace_bytes": [_i64, _i64, _i64, _i64, _i32],
 }
 STRING_FUNCS = {"qvit_strerror": [_i32], "qvit_version": []}
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + list(INT64_FUNCS) + list(STRING_FUNCS))
@@ -995,3 +1004,82 @@ def conv_wgrad(G: torch.Tensor, x: torch.Tensor, kernel_size, stride, padding, d
                                _ptr(out), _ptr(workspace), workspace.numel() * workspace.element_size(),
                                _stream(G.device)), "qvit_conv_wgrad")
     return out
+
+
+# ---- UltraNet training: BatchNorm2d -> quantizer -> max pool (ultra_bn_fuse.hip) ------------------------------
+def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
+    _require_gpu(t, name)
+    t = t.detach()
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+
+
+def _workspace(nbytes: int, what: str, workspace: Optional[torch.Tensor], dev) -> torch.Tensor:
+    if nbytes < 0:
+        _check(nbytes, what)
+    if workspace is None:
+        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    return workspace
+
+
+def bn_stats(x: torch.Tensor, eps: float, factor: float = 0.0, running_mean: Optional[torch.Tensor] = None,
+             running_var: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """Batch statistics of x [B, C, H, W] per channel (qvit_bn_stats): (mean, biased var, invstd), fp32 [C] each;
+    the running tensors, when given, are updated in place as nn.BatchNorm2d does with `factor`."""
+    x = _f32c(x, "input")
+    B, C, H, W = x.shape
+    lib = load()
+    ws = _workspace(int(lib.qvit_bn_stats_workspace_bytes(B, C, H, W)), "qvit_bn_stats_workspace_bytes", workspace,
+                    x.device)
+    for r in (running_mean, running_var):
+        assert r is None or (r.is_cuda and r.dtype == torch.float32 and r.is_contiguous() and r.numel() == C)
+    stats = torch.empty((3, C), dtype=torch.float32, device=x.device)
+    _check(lib.qvit_bn_stats(_ptr(x), B, C, H, W, float(eps), float(factor), _ptr(running_mean), _ptr(running_var),
+                             _ptr(stats[0]), _ptr(stats[1]), _ptr(stats[2]), _ptr(ws),
+                             ws.numel() * ws.element_size(), _stream(x.device)), "qvit_bn_stats")
+    return stats[0], stats[1], stats[2]
+
+
+def bn_act_pool_forward(x: torch.Tensor, mean: torch.Tensor, invstd: torch.Tensor, gamma: Optional[torch.Tensor],
+                        beta: Optional[torch.Tensor], levels: int, pool: bool):
+    """quantizer(batch_norm(x)) on the given statistics, max-pooled 2 x 2 when `pool` (qvit_bn_act_pool_forward):
+    (values k / levels, flag bytes), both shaped as the output."""
+    x = _f32c(x, "input")
+    B, C, H, W = x.shape
+    shape = (B, C, H // 2, W // 2) if pool else (B, C, H, W)
+    out = torch.empty(shape, dtype=torch.float32, device=x.device)
+    flags = torch.empty(shape, dtype=torch.uint8, device=x.device)
+    gamma = None if gamma is None else _f32c(gamma, "gamma")
+    beta = None if beta is None else _f32c(beta, "beta")
+    _check(load().qvit_bn_act_pool_forward(_ptr(x), B, C, H, W, _ptr(mean), _ptr(invstd), _ptr(gamma), _ptr(beta),
+                                           int(levels), int(bool(pool)), _ptr(out), _ptr(flags), _stream(x.device)),
+           "qvit_bn_act_pool_forward")
+    return out, flags
+
+
+def bn_act_pool_backward(x: torch.Tensor, grad_out: torch.Tensor, flags: torch.Tensor, mean: torch.Tensor,
+                         invstd: torch.Tensor, gamma: Optional[torch.Tensor], pool: bool, want_dgamma: bool = True,
+                         want_dbeta: bool = True, workspace: Optional[torch.Tensor] = None):
+    """Backward of bn_act_pool_forward over x given its flag bytes (qvit_bn_act_pool_backward_reduce, then
+    qvit_bn_act_pool_backward_dx): (dx, dgamma or None, dbeta or None, sums [2, C] float64 = S1, S2)."""
+    x = _f32c(x, "input")
+    g = _f32c(grad_out, "grad_out")
+    B, C, H, W = x.shape
+    pool = int(bool(pool))
+    if tuple(g.shape) != tuple(flags.shape) or tuple(g.shape) != ((B, C, H // 2, W // 2) if pool else (B, C, H, W)):
+        raise QvitError(f"bn_act_pool_backward: grad_out {tuple(g.shape)}, flags {tuple(flags.shape)} for an input "
+                        f"of {tuple(x.shape)}, pool {pool}")
+    lib = load()
+    ws = _workspace(int(lib.qvit_bn_act_pool_backward_workspace_bytes(B, C, H, W, pool)),
+                    "qvit_bn_act_pool_backward_workspace_bytes", workspace, x.device)
+    sums = torch.empty((2, C), dtype=torch.float64, device=x.device)
+    _check(lib.qvit_bn_act_pool_backward_reduce(_ptr(x), _ptr(g), _ptr(flags), B, C, H, W, _ptr(mean), _ptr(invstd),
+                                                pool, _ptr(sums), _ptr(ws), ws.numel() * ws.element_size(),
+                                                _stream(x.device)), "qvit_bn_act_pool_backward_reduce")
+    dx = torch.empty_like(x)
+    dgamma = torch.empty(C, dtype=torch.float32, device=x.device) if want_dgamma else None
+    dbeta = torch.empty(C, dtype=torch.float32, device=x.device) if want_dbeta else None
+    gamma = None if gamma is None else _f32c(gamma, "gamma")
+    _check(lib.qvit_bn_act_pool_backward_dx(_ptr(x), _ptr(g), _ptr(flags), B, C, H, W, _ptr(mean), _ptr(invstd),
+                                            _ptr(gamma), _ptr(sums), pool, _ptr(dx), _ptr(dgamma), _ptr(dbeta),
+                                            _stream(x.device)), "qvit_bn_act_pool_backward_dx")
+    return dx, dgamma, dbeta, sums

@@ -26,6 +26,9 @@ gradient as qvit_conv_wonly / qvit_gemm_wonly on the transposed (and, for a conv
 gradient as qvit_conv_wgrad when the caller states that the input holds activation codes (`in_levels`).
 QVIT_ULTRA_BWD=hip|torch|dgrad|wgrad selects which of the two contractions run on these kernels (torch: both on
 the library; the quantizer backwards stay in HIP).
+
+QVIT_ULTRA_TRAIN_FUSE=1 (default 0) lets UltraNetQua.forward_modules run each training-mode
+BatchNorm2d -> activation_quantize_fn (-> MaxPool2d(2, 2)) run as one node, bn_act_pool, on ultra_bn_fuse.hip.
 """
 from __future__ import annotations
 
@@ -58,6 +61,20 @@ DGRAD_HIP_MAX_PIXELS = 64 * 64
 _ULTRA_BWD_OPS = {"hip": ("dgrad", "wgrad"), "torch": (), "dgrad": ("dgrad",), "wgrad": ("wgrad",)}
 if ULTRA_BWD not in _ULTRA_BWD_OPS:
     raise ValueError(f"QVIT_ULTRA_BWD={ULTRA_BWD!r}: expected hip, torch, dgrad or wgrad")
+
+
+# "1": UltraNetQua.forward_modules routes BatchNorm2d (batch statistics) -> activation_quantize_fn -> MaxPool2d(2, 2)
+# through bn_act_pool under autograd. Off by default: the fused y = fmaf(x - mean, gamma invstd, beta) is not ATen's
+# batch-norm arithmetic bit for bit, so a code at a rounding tie may differ from the module route's.
+ULTRA_TRAIN_FUSE = os.environ.get("QVIT_ULTRA_TRAIN_FUSE", "0")
+if ULTRA_TRAIN_FUSE not in ("0", "1"):
+    raise ValueError(f"QVIT_ULTRA_TRAIN_FUSE={ULTRA_TRAIN_FUSE!r}: expected 0 or 1")
+
+
+def train_fuse_enabled() -> bool:
+    if ULTRA_TRAIN_FUSE not in ("0", "1"):
+        raise ValueError(f"ULTRA_TRAIN_FUSE = {ULTRA_TRAIN_FUSE!r}: expected 0 or 1")
+    return ULTRA_TRAIN_FUSE == "1"
 
 
 def _backward_gemm_ops() -> tuple:
@@ -123,6 +140,66 @@ class _ActQuantSTE(torch.autograd.Function):
     def backward(ctx, grad_output):
         (x,) = ctx.saved_tensors
         return _lib.ultra_act_quant_backward(x, grad_output).reshape(x.shape).to(x.dtype), None
+
+
+class _BnActPoolFunction(torch.autograd.Function):
+    """BatchNorm2d on batch statistics -> activation_quantize_fn -> optional MaxPool2d(2, 2) as one node
+    (ultra_bn_fuse.hip). Saved for the backward: x, mean, invstd, one flag byte per output
+    element (the clamp's pass bit and, pooled, the window's winner) and gamma; no batch-norm output, no quantizer
+    input, no pool indices. The backward recomputes xhat from x."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, mean, invstd, levels, pool):
+        out, flags = _lib.bn_act_pool_forward(x, mean, invstd, gamma, beta, levels, pool)
+        ctx.save_for_backward(x, mean, invstd, flags, gamma)
+        ctx.pool = pool
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, mean, invstd, flags, gamma = ctx.saved_tensors
+        need_x, need_g, need_b = ctx.needs_input_grad[:3]
+        dx, dgamma, dbeta, _ = _lib.bn_act_pool_backward(x, grad_out, flags, mean, invstd, gamma, ctx.pool,
+                                                         need_g, need_b)
+        return (dx.to(x.dtype) if need_x else None, dgamma if need_g else None, dbeta if need_b else None, None, None,
+                None, None)
+
+
+def _pool_fits(pool) -> bool:
+    pair = lambda v: tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+    return (isinstance(pool, nn.MaxPool2d) and pair(pool.kernel_size) == (2, 2) and pair(pool.stride) == (2, 2)
+            and pair(pool.padding) == (0, 0) and pair(pool.dilation) == (1, 1) and not pool.ceil_mode
+            and not pool.return_indices)
+
+
+def bn_act_pool(x: torch.Tensor, bn, act, pool=None):
+    """pool(act(bn(x))) for an nn.BatchNorm2d on batch statistics (training mode, or no running statistics), an
+    activation_quantize_fn with 1 <= a_bit <= 7 and `pool` None or MaxPool2d(2, 2): qvit_bn_stats (which also makes
+    the module's running-statistics update; num_batches_tracked is bumped here), then one autograd node,
+    _BnActPoolFunction. x: a 4-D fp32 ROCm tensor. Returns None when the modules do not fit (the caller then runs
+    them one by one)."""
+    if not (type(bn) is nn.BatchNorm2d and (bn.training or (bn.running_mean is None and bn.running_var is None))
+            and isinstance(act, activation_quantize_fn) and 1 <= act.a_bit <= 7
+            and (pool is None or _pool_fits(pool))
+            and isinstance(x, torch.Tensor) and x.dim() == 4 and x.is_cuda and x.dtype == torch.float32
+            and x.shape[1] == bn.num_features and x.numel() > 0):
+        return None
+    B, C, H, W = x.shape
+    if B * H * W < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.size()}")
+    if pool is not None and (H < 2 or W < 2):
+        return None
+    factor, rmean, rvar = 0.0, None, None
+    if bn.training and bn.track_running_stats:   # nn.BatchNorm2d.forward
+        if bn.num_batches_tracked is not None:
+            bn.num_batches_tracked.add_(1)
+            factor = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
+        else:
+            factor = 0.0 if bn.momentum is None else bn.momentum
+        rmean, rvar = bn.running_mean, bn.running_var
+    xc = x if x.is_contiguous() else x.contiguous()
+    mean, _, invstd = _lib.bn_stats(xc, bn.eps, factor, rmean, rvar)
+    return _BnActPoolFunction.apply(xc, bn.weight, bn.bias, mean, invstd, 2 ** act.a_bit - 1, pool is not None)
 
 
 def _round_up(v: int, m: int) -> int:

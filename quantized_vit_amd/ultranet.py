@@ -21,7 +21,7 @@ from typing import Optional
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, quant_ultra
 from .quant_ultra import activation_quantize_fn, conv2d_Q_fn
 from .vit_model import _timed   # benchmark event hooks (vit_model.KERNEL_TIMING)
 
@@ -225,14 +225,27 @@ class UltraNetQua(nn.Module):
         forward, with the reference's straight-through backward (quant_ultra.py). This walk
         knows what feeds each conv: an activation_quantize_fn with a_bit <= 7, max-pooled or not, leaves values
         k / (2^a_bit - 1), and the conv is told so (`_in_levels`), which puts its weight gradient on
-        qvit_conv_wgrad; BatchNorm2d and MaxPool2d train on ATen."""
+        qvit_conv_wgrad; BatchNorm2d and MaxPool2d train on ATen, unless QVIT_ULTRA_TRAIN_FUSE=1: then, under grad
+        mode, every unhooked training-mode BatchNorm2d -> activation_quantize_fn (-> MaxPool2d(2, 2)) run is one
+        node on ultra_bn_fuse.hip (quant_ultra.bn_act_pool)."""
         img_size = x.shape[-2:]
         yolo_out = []
         with _aten_batch_norm():
             mods, i = list(self.layers), 0
             levels = None   # the input holds k / levels (what the module before this one wrote), if known
+            fuse = quant_ultra.train_fuse_enabled() and torch.is_grad_enabled()
             while i < len(mods):
                 m = mods[i]
+                if fuse and isinstance(m, nn.BatchNorm2d) and i + 1 < len(mods) and \
+                        isinstance(mods[i + 1], activation_quantize_fn):
+                    y, n = None, 3
+                    if i + 2 < len(mods) and isinstance(mods[i + 2], nn.MaxPool2d) and not _hooked(mods[i:i + 3]):
+                        y = quant_ultra.bn_act_pool(x, m, mods[i + 1], mods[i + 2])
+                    if y is None and not _hooked(mods[i:i + 2]):
+                        y, n = quant_ultra.bn_act_pool(x, m, mods[i + 1]), 2
+                    if y is not None:
+                        x, i, levels = y, i + n, 2 ** mods[i + 1].a_bit - 1
+                        continue
                 if hasattr(m, "forward_bn_act") and i + 2 < len(mods) and not _hooked(mods[i:i + 3]):
                     y = m.forward_bn_act(x, mods[i + 1], mods[i + 2])   # conv -> BN -> quantizer in one launch
                     if y is not None:
