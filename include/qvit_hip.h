@@ -472,7 +472,8 @@ int qvit_epi_table_build(int epilogue, int out_qtype, const float* out_d, const 
  * (reference vit_model.py:133-149): out = softmax((q @ k^T) * scale) @ v per (image, head),
  * written as [B*N][ldo] with column h*head_dim + d (the reference's transpose(1, 2).reshape).
  *   qkv      : fp32 [B*N][ldq], row = [q | k | v], each H*head_dim wide (qkv.reshape(B,N,3,H,hd)).
- *   head_dim : 64 (the only supported head size); scale: qk_scale (head_dim ** -0.5 by default).
+ *   head_dim : 64, or 80 with QVIT_ATT_F32 (80 with QVIT_ATT_I8, or any other size: QVIT_EINVAL);
+ *              ldq >= 3 H head_dim, ldo >= H head_dim. scale: qk_scale (head_dim ** -0.5 by default).
  *   in_scale : power of two applied to q, k, v before their fp16 hi/lo split (keeps |x * in_scale|
  *              < 65504; undone exactly), 1.0 for ordinary activations.
  *   out_mode : QVIT_ATT_F32 -> fp32 out (ldo % 4 == 0, 16-B aligned);
@@ -659,17 +660,19 @@ int qvit_attention(const float* qkv, int64_t B, int64_t N, int64_t H, int64_t he
  * with S = scale q k^T, P = softmax(S), O = P v and D_i = sum_c dO_ic O_ic,
  *   dv = P^T dO,  dS = P o (dO v^T - D),  dq = scale dS k,  dk = scale dS^T q.
  * S and P are recomputed per 32-row block on chip; nothing N x N reaches global memory.
- *   qkv      : fp32 [B N][ldq], the forward's input (q, k, v sections of H * 64 columns); ldq >= 3 H 64
- *   out      : fp32 [B N][ldo], the forward's output O (required); ldo >= H 64
- *   grad_out : fp32 [B N][ldgo], dO; ldgo >= H 64
- *   grad_qkv : fp32 [B N][ldg], written in the layout of qkv (columns [0, 3 H 64) only); ldg >= 3 H 64
+ * With hd = head_dim:
+ *   qkv      : fp32 [B N][ldq], the forward's input (q, k, v sections of H * hd columns); ldq >= 3 H hd
+ *   out      : fp32 [B N][ldo], the forward's output O (required); ldo >= H hd
+ *   grad_out : fp32 [B N][ldgo], dO; ldgo >= H hd
+ *   grad_qkv : fp32 [B N][ldg], written in the layout of qkv (columns [0, 3 H hd) only); ldg >= 3 H hd
  *   in_scale : the forward's power of two (|qkv in_scale| <= 16384)
  *   g_scale  : a power of two with |grad_out g_scale| <= 16384, as close to it as the caller can make it (gradients
  *              of 1e-8 would flush in the fp16 operand split); undone exactly, so grad(a dO) = a grad(dO) bit for
  *              bit for a power of two a when g_scale follows max |dO|
  *   workspace: qvit_attention_backward_workspace_bytes(B, N, H) bytes (O(B H N): one log-sum-exp and one D per
  *              query, one bound per head), 16-byte aligned, caller-owned, no state carried between calls.
- * head_dim must be 64; every pointer 16-byte aligned and every leading dimension a multiple of 4. Three launches
+ * head_dim must be 64 or 80 (the workspace does not depend on it); every pointer 16-byte aligned and
+ * every leading dimension a multiple of 4. Three launches
  * (row sums, query owner -> dq, key owner -> dk, dv), no float atomics: a call is bitwise reproducible.
  * qvit_attention_backward_workspace_bytes returns QVIT_EINVAL for N <= 0, H <= 0 or B < 0.
  */

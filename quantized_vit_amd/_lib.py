@@ -694,7 +694,8 @@ def epi_table_build(epilogue: int, out_qtype: int, out_d, out_qm, out_t, out_lev
 def attention(qkv: torch.Tensor, B: int, N: int, H: int, head_dim: int, scale: float, out: torch.Tensor,
               out_mode: int = ATT_F32, in_scale: float = 1.0, out_qtype: int = 0, out_d=None, out_qm=None,
               out_t=None, out_levels: int = 0) -> torch.Tensor:
-    """softmax(q k^T * scale) v per (image, head) on a [B*N, >= 3*H*hd] fp32 qkv projection."""
+    """softmax(q k^T * scale) v per (image, head) on a [B*N, >= 3*H*hd] fp32 qkv projection; hd 64, or 80 with
+    ATT_F32 (anything else is QVIT_EINVAL)."""
     _require_gpu(qkv, "qkv")
     assert qkv.dtype == torch.float32 and qkv.stride(1) == 1
     _check(load().qvit_attention(_ptr(qkv), B, N, H, head_dim, qkv.stride(0), scale, in_scale, out_mode, _ptr(out),
@@ -710,7 +711,7 @@ def attention_backward_workspace_bytes(B: int, N: int, H: int) -> int:
 def attention_backward(qkv: torch.Tensor, out: torch.Tensor, grad_out: torch.Tensor, B: int, N: int, H: int,
                        head_dim: int, scale: float, in_scale: float = 1.0, g_scale: float = 1.0,
                        grad_qkv: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Gradient of attention() with respect to qkv (qvit_attention_backward): qkv [B*N, >= 3*H*hd], out and
+    """Gradient of attention() with respect to qkv (qvit_attention_backward; hd 64 or 80): qkv [B*N, >= 3*H*hd], out and
     grad_out [B*N, >= H*hd], all fp32 with unit column stride. Returns grad_qkv shaped like qkv's [B*N, 3*H*hd]
     columns (written into `grad_qkv` when given; columns past 3*H*hd are left alone)."""
     for t, name in ((qkv, "qkv"), (out, "out"), (grad_out, "grad_out")):

@@ -22,6 +22,8 @@
 // LDS images (128-B rows of 64 fp16), XOR-swizzled, conflict-free for every read and write:
 //   K: 16-B chunk c of row r at c ^ ((r >> 1) & 7)        (ds_read_b128 A fragments)
 //   V: 32-B block b of row r at b ^ ((r >> 1) & 3)        (ds_read_b64_tr_b16 transposed reads)
+// attn_kernel also has a head dim 80 instantiation (fp32 output; ViT-Huge/14): 64 + 16 columns, the 16 in tail
+// images and a K = 16 MFMA step (attn_common.h), 3 query tiles per wave.
 #include "attn_common.h"
 
 #include <algorithm>
@@ -42,36 +44,47 @@ QVIT_DEV void attend_n(int nt, bool mask, const int8_t* st, const h8 (&qh)[QTW][
 }
 
 // ---- fp32 qkv input (the unfused module path) -------------------------------------------------------
-template <int OUT>  // 0: fp32 output, 1: int8 codes of the next layer's activation quantizer
+// D: head dim, 64 or 80. At 80 (attn_common.h: 64 + 16 columns) a stage has four 1-KiB tail images behind its
+// four images (20 KiB, 40 KiB per workgroup: two workgroups per CU as at 64), a wave carries a fifth accumulator
+// slice and the queries' 16 tail columns per tile, and threads 0 .. 127 stage the tails (row tid >> 2, 4 columns).
+// QT: query tiles per wave; the workgroup owns NWAVES * QT * 16 queries.
+template <int D>
+constexpr int stage_bytes = 4 * IMG + (D == HD80 ? 4 * TAIL : 0);
+
+// OUT 0: fp32 output, 1: int8 codes of the next layer's activation quantizer
+template <int OUT, int D = HD, int QT = QTW>
 __global__ __launch_bounds__(256, 2) void attn_kernel(const float* __restrict__ qkv, int N, int H, int64_t ldq,
                                                       float scale, float in_scale, void* __restrict__ out,
                                                       int64_t ldo, int out_qtype, const float* out_d,
                                                       const float* out_qm, const float* out_t, int out_levels) {
-  __shared__ __attribute__((aligned(16))) int8_t smem[2 * STAGE];
+  constexpr int QGRP = NWAVES * QT * 16;      // queries per workgroup
+  constexpr int STG = stage_bytes<D>;
+  __shared__ __attribute__((aligned(16))) int8_t smem[2 * STG];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int fr = lane & 15;
   const int g = lane >> 4;
 
-  const int ngroups = (N + QG - 1) / QG;
+  const int ngroups = (N + QGRP - 1) / QGRP;
   const int bid = blockIdx.x;
   const int grp = bid % ngroups;
   const int bh = bid / ngroups;
   const int h = bh % H;
   const int b = bh / H;
-  const int C = H * HD;
+  const int C = H * D;
   const float* base = qkv + (int64_t)b * N * ldq;
-  const float* qcol = base + h * HD;
-  const float* kcol = base + C + h * HD;
-  const float* vcol = base + 2 * C + h * HD;
+  const float* qcol = base + h * D;
+  const float* kcol = base + C + h * D;
+  const float* vcol = base + 2 * C + h * D;
 
   // ---- Q^T fragments (B operand): lane holds Q[q][8g .. 8g+7] (+32) ------------------------------
-  const int q0 = grp * QG;
-  h8 qh[QTW][2], ql[QTW][2];
-  bool tv[QTW];
+  const int q0 = grp * QGRP;
+  h8 qh[QT][2], ql[QT][2];
+  [[maybe_unused]] TailFrag<QT, D> qt;
+  bool tv[QT];
 #pragma unroll
-  for (int i = 0; i < QTW; ++i) {
+  for (int i = 0; i < QT; ++i) {
     const int tile = wave + NWAVES * i;
     tv[i] = q0 + 16 * tile < N;  // wave-uniform
     int q = q0 + 16 * tile + fr;
@@ -85,11 +98,15 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const float* __restrict__ 
       for (int j = 0; j < 4; ++j) { x[j] = a[j] * in_scale; x[4 + j] = bq[j] * in_scale; }
       split8(x, qh[i][c], ql[i][c]);
     }
+    if constexpr (D == HD80)  // columns 64 + 4 g .. + 3: the B operand of the K = 16 step
+      split4(*reinterpret_cast<const f4*>(qcol + (int64_t)q * ldq + 64 + 4 * g) * in_scale, qt.h[i], qt.l[i]);
   }
 
   // ---- key-block staging: thread -> key row tid >> 3 (0..31), 8-dim chunk tid & 7 ------------------
   const int srow = tid >> 3, schunk = tid & 7;
   f4 pk[2], pv[2];
+  [[maybe_unused]] f4 tk, tvv;                    // head dim 80: columns 64 + 4 (tid & 3) .. + 3 of key row tid >> 2
+  [[maybe_unused]] const bool stail = tid < 128;  // wave-uniform (waves 0 and 1)
   auto load_block = [&](int kb) {
     const int key = kb * KB + srow;
     if (key < N) {
@@ -100,9 +117,19 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const float* __restrict__ 
     } else {
       pk[0] = pk[1] = pv[0] = pv[1] = f4{0.f, 0.f, 0.f, 0.f};
     }
+    if constexpr (D == HD80) {
+      if (stail) {
+        const int tkey = kb * KB + (tid >> 2);
+        tk = tvv = f4{0.f, 0.f, 0.f, 0.f};
+        if (tkey < N) {
+          tk = *reinterpret_cast<const f4*>(kcol + (int64_t)tkey * ldq + 64 + 4 * (tid & 3));
+          tvv = *reinterpret_cast<const f4*>(vcol + (int64_t)tkey * ldq + 64 + 4 * (tid & 3));
+        }
+      }
+    }
   };
   auto store_block = [&](int buf) {
-    int8_t* st = smem + buf * STAGE;
+    int8_t* st = smem + buf * STG;
     float x[8];
     h8 hi, lo;
 #pragma unroll
@@ -115,6 +142,17 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const float* __restrict__ 
     split8(x, hi, lo);
     *reinterpret_cast<h8*>(st + 2 * IMG + voff(srow, 16 * schunk)) = hi;
     *reinterpret_cast<h8*>(st + 3 * IMG + voff(srow, 16 * schunk)) = lo;
+    if constexpr (D == HD80) {
+      if (stail) {  // 8 tid = 32 (tid >> 2) + 8 (tid & 3): the tail's byte offset of this thread's 4 columns
+        h4 th, tl;
+        split4(tk * in_scale, th, tl);
+        *reinterpret_cast<h4*>(st + 4 * IMG + 8 * tid) = th;
+        *reinterpret_cast<h4*>(st + 4 * IMG + TAIL + 8 * tid) = tl;
+        split4(tvv * in_scale, th, tl);
+        *reinterpret_cast<h4*>(st + 4 * IMG + 2 * TAIL + 8 * tid) = th;
+        *reinterpret_cast<h4*>(st + 4 * IMG + 3 * TAIL + 8 * tid) = tl;
+      }
+    }
   };
 
   int koffs[2][2], voffs[4];
@@ -122,19 +160,19 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const float* __restrict__ 
 
   // softmax state and O^T accumulators: o[i][dt][j] = O^T[16 dt + 4 g + j][query of lane]
   const float sl2 = scale * LOG2E / (in_scale * in_scale);
-  float m[QTW], l[QTW];
-  f4 o[QTW][4];
+  float m[QT], l[QT];
+  f4 o[QT][D / 16];
 #pragma unroll
-  for (int i = 0; i < QTW; ++i) {
+  for (int i = 0; i < QT; ++i) {
     m[i] = -INFINITY;
     l[i] = 0.f;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[i][dt] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < D / 16; ++dt) o[i][dt] = f4{0.f, 0.f, 0.f, 0.f};
   }
 
-  int nt = 0;  // valid tiles of this wave (a prefix of i = 0..3)
+  int nt = 0;  // valid tiles of this wave (a prefix of i = 0 .. QT - 1)
 #pragma unroll
-  for (int i = 0; i < QTW; ++i) nt += tv[i] ? 1 : 0;
+  for (int i = 0; i < QT; ++i) nt += tv[i] ? 1 : 0;
   const int nkb = (N + KB - 1) / KB;
   load_block(0);
   store_block(0);
@@ -142,8 +180,8 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const float* __restrict__ 
   for (int kb = 0; kb < nkb; ++kb) {
     if (kb + 1 < nkb) load_block(kb + 1);
     Stamps sp;
-    attend_n(nt, (kb + 1) * KB > N, smem + (kb & 1) * STAGE, qh, ql, m, l, o, koffs, voffs, kb * KB + 4 * g, N,
-             sl2, sp);
+    attend<QT, IMG, false, D>(nt, (kb + 1) * KB > N, smem + (kb & 1) * STG, qh, ql, m, l, o, koffs, voffs,
+                               kb * KB + 4 * g, N, sl2, sp, qt);
     if (kb + 1 < nkb) {
       __syncthreads();  // every wave is done with buffer (kb + 1) & 1 (used by block kb - 1)
       store_block((kb + 1) & 1);
@@ -153,9 +191,14 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const float* __restrict__ 
   QParams qp{};
   if (OUT == 1) qp = load_qparams(out_qtype, out_d, out_qm, out_t, out_levels);
   const bool st16 = ((ldo & 15) == 0) && ((((uintptr_t)out) & 15) == 0);
-  attend_store<OUT, QTW>(tv, l, o, wave, NWAVES, q0, N, b, h, in_scale, out, ldo, qp, EpiLds{nullptr, 0.f, 0.f, 0.f},
-                         st16);
+  attend_store<OUT, QT, D>(tv, l, o, wave, NWAVES, q0, N, b, h, in_scale, out, ldo, qp,
+                            EpiLds{nullptr, 0.f, 0.f, 0.f}, st16);
 }
+
+// head dim 80, fp32 output only: 3 query tiles per wave (192 queries per workgroup); 4 do not fit in 256
+// registers
+constexpr int QTW80 = 3;
+constexpr int QG80 = NWAVES * QTW80 * 16;
 
 // ---- split fp16 input (the fused block path) --------------------------------------------------------
 // q, k, v arrive pre-scaled and pre-split by the qkv GEMM (qvit_gemm_qkv_split): hi and lo planes of
@@ -346,8 +389,9 @@ extern "C" int qvit_attention(const float* qkv, int64_t B, int64_t N, int64_t H,
                               const float* out_d, const float* out_qm, const float* out_t, int out_levels,
                               hipStream_t stream) {
   if (!qkv || !out) return QVIT_ENULL;
-  if (head_dim != HD) return QVIT_EINVAL;
-  if (B < 0 || N <= 0 || H <= 0 || ldq < 3 * H * HD || ldo < H * HD) return QVIT_EINVAL;
+  if (head_dim != HD && head_dim != HD80) return QVIT_EINVAL;
+  if (head_dim == HD80 && out_mode != QVIT_ATT_F32) return QVIT_EINVAL;  // the int8 epilogue is for head dim 64
+  if (B < 0 || N <= 0 || H <= 0 || ldq < 3 * H * head_dim || ldo < H * head_dim) return QVIT_EINVAL;
   if (B * N > INT32_MAX || N > (1 << 20) || !(in_scale > 0.f)) return QVIT_EINVAL;
   if ((ldq % 4) || (((uintptr_t)qkv) & 15)) return QVIT_EALIGN;
   if (out_mode == QVIT_ATT_F32) {
@@ -361,10 +405,13 @@ extern "C" int qvit_attention(const float* qkv, int64_t B, int64_t N, int64_t H,
     return QVIT_EINVAL;
   }
   if (B == 0) return QVIT_OK;
-  const int64_t ngroups = (N + QG - 1) / QG;
+  const int64_t ngroups = head_dim == HD80 ? (N + QG80 - 1) / QG80 : (N + QG - 1) / QG;
   const int64_t nblk = B * H * ngroups;
   if (nblk > INT32_MAX) return QVIT_EINVAL;
-  if (out_mode == QVIT_ATT_F32)
+  if (head_dim == HD80)
+    hipLaunchKernelGGL((attn_kernel<0, HD80, QTW80>), dim3((unsigned)nblk), dim3(256), 0, stream, qkv, (int)N, (int)H,
+                       ldq, scale, in_scale, out, ldo, out_qtype, out_d, out_qm, out_t, out_levels);
+  else if (out_mode == QVIT_ATT_F32)
     hipLaunchKernelGGL(attn_kernel<0>, dim3((unsigned)nblk), dim3(256), 0, stream, qkv, (int)N, (int)H, ldq, scale,
                        in_scale, out, ldo, out_qtype, out_d, out_qm, out_t, out_levels);
   else

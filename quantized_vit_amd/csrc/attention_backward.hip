@@ -36,6 +36,10 @@ using namespace qvit_attn;
 constexpr int NWAVES = 4;
 constexpr int TW = 2;                    // owner tiles (16 rows) per wave
 constexpr int OG = NWAVES * TW * 16;     // owner rows per workgroup (128)
+// head dim 80: the query owner keeps two tiles per wave; the key owner, whose two
+// accumulators per tile grow to 40 registers, fits only one in 256 registers (64 keys per workgroup)
+constexpr int TWQ80 = 2;
+constexpr int TWK80 = 1;
 constexpr int P_SHIFT = 14;              // the key owner's P operand is 2^14 P
 
 // Workspace: [T: B H floats, padded to 4][lse: B H Np][D: B H Np], Np = N rounded up to 32 (float4 reads of a
@@ -60,6 +64,9 @@ QVIT_DEV float max8(const float (&r)[8]) {
 }
 
 // ---- 1. D and the dS bound -----------------------------------------------------------------------------
+// A row is read as 4 parts of D / 4 columns (16 at head dim 64, 20 at 80: five 16-B loads, 80-B aligned), each
+// part summed left to right by one lane, the 4 parts folded by the same butterfly: the order is fixed at both widths.
+template <int D = HD>
 __global__ __launch_bounds__(256) void bwd_prep_kernel(const float* __restrict__ qkv, const float* __restrict__ out,
                                                        const float* __restrict__ gout, int N, int H, int64_t ldq,
                                                        int64_t ldo, int64_t ldgo, float in_scale, float g_scale,
@@ -68,7 +75,8 @@ __global__ __launch_bounds__(256) void bwd_prep_kernel(const float* __restrict__
   const int tid = threadIdx.x;
   const int bh = blockIdx.x;
   const int h = bh % H, b = bh / H;
-  const int C = H * HD;
+  constexpr int PW = D / 4;  // columns per part
+  const int C = H * D;
   const int64_t Np = np_of(N);
   float* Dw = ws + hdr_of((int64_t)gridDim.x) + ((int64_t)gridDim.x + bh) * Np;
   const int part = tid & 3;
@@ -78,11 +86,11 @@ __global__ __launch_bounds__(256) void bwd_prep_kernel(const float* __restrict__
     float dsum = 0.f, g2 = 0.f, v2 = 0.f;
     if (row < N) {
       const int64_t R = (int64_t)b * N + row;
-      const f4* gp = reinterpret_cast<const f4*>(gout + R * ldgo + h * HD + 16 * part);
-      const f4* op = reinterpret_cast<const f4*>(out + R * ldo + h * HD + 16 * part);
-      const f4* vp = reinterpret_cast<const f4*>(qkv + R * ldq + 2 * C + h * HD + 16 * part);
+      const f4* gp = reinterpret_cast<const f4*>(gout + R * ldgo + h * D + PW * part);
+      const f4* op = reinterpret_cast<const f4*>(out + R * ldo + h * D + PW * part);
+      const f4* vp = reinterpret_cast<const f4*>(qkv + R * ldq + 2 * C + h * D + PW * part);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
+      for (int k = 0; k < PW / 4; ++k) {
         const f4 gv = gp[k] * g_scale, ov = op[k] * in_scale, vv = vp[k] * in_scale;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -144,8 +152,26 @@ QVIT_DEV void put(int8_t* img, int off, h8 hi, h8 lo) {
   *reinterpret_cast<h8*>(img + IMG + off) = lo;
 }
 
-// the owner's own rows as B operands: lane holds X[row][32 c + 8 g .. + 7] * sc
-QVIT_DEV void load_own(const float* col, int64_t ld, int row, float sc, h8 (&hi)[2], h8 (&lo)[2]) {
+// Head dim 80 (attn_common.h: 64 + 16 columns): threads 0 .. 127 also stage a block's columns 64 .. 79 (row
+// tid >> 2, 4 columns each) into the section's tail image pair; 8 tid is that thread's byte offset in it.
+QVIT_DEV f4 load_tail(const float* col, int64_t ld, int row, int N) {
+  const int tid = threadIdx.x;
+  if (row >= N) return f4{0.f, 0.f, 0.f, 0.f};
+  return *reinterpret_cast<const f4*>(col + (int64_t)row * ld + 64 + 4 * (tid & 3));
+}
+
+QVIT_DEV void put_tail(int8_t* tail, f4 x, float sc) {
+  h4 hi, lo;
+  split4(x * sc, hi, lo);
+  *reinterpret_cast<h4*>(tail + 8 * threadIdx.x) = hi;
+  *reinterpret_cast<h4*>(tail + TAIL + 8 * threadIdx.x) = lo;
+}
+
+// the owner's own rows as B operands: lane holds X[row][32 c + 8 g .. + 7] * sc, and at head dim 80
+// X[row][64 + 4 g .. + 3] * sc in tile i of yt
+template <int D, int T>
+QVIT_DEV void load_own(const float* col, int64_t ld, int row, float sc, h8 (&hi)[2], h8 (&lo)[2], TailFrag<T, D>& yt,
+                       int i) {
   const int g = (threadIdx.x & 63) >> 4;
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
@@ -153,24 +179,40 @@ QVIT_DEV void load_own(const float* col, int64_t ld, int row, float sc, h8 (&hi)
     Chunk ch{src[0], src[1]};
     split_chunk(ch, sc, hi[c], lo[c]);
   }
+  if constexpr (D == HD80)
+    split4(*reinterpret_cast<const f4*>(col + (int64_t)row * ld + 64 + 4 * g) * sc, yt.h[i], yt.l[i]);
 }
 
 // X^T . Y^T for one block: A fragments of the 32 block rows from the koff image pair at img (hi, lo),
 // B the owner's rows: res[kt][j] = sum_d X[16 kt + 4 g + j][d] Y[row of the lane][d]
-QVIT_DEV void rows_dot(const int8_t* img, const int (&koffs)[2][2], const h8 (&yh)[2], const h8 (&yl)[2],
-                       f4 (&res)[2]) {
+// (head dim 80: d = 64 .. 79 last, one K = 16 step on the tail image pair at tail and tile i of yt)
+template <int D, int T>
+QVIT_DEV void rows_dot(const int8_t* img, const int8_t* tail, const int (&koffs)[2][2], const h8 (&yh)[2],
+                       const h8 (&yl)[2], const TailFrag<T, D>& yt, int i, f4 (&res)[2]) {
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
     res[kt] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < 2; ++c)
       res[kt] = mfma3(lds_h8(img, koffs[kt][c]), lds_h8(img + IMG, koffs[kt][c]), yh[c], yl[c], res[kt]);
+    if constexpr (D == HD80) {
+      const int lane = threadIdx.x & 63;
+      const int off = ktoff(16 * kt + (lane & 15), lane >> 4);
+      // summed from zero in an accumulator of its own and added on the VALU: the K = 16 instruction never takes
+      // the K = 32 instruction's fresh result as its SrcC. Chained, the sums here were wrong and varied from run to
+      // run (observed; cause not isolated, missing hazard wait states suspected: attn_common.h mfma3t)
+      res[kt] = res[kt] + mfma3t(lds_h4(tail, off), lds_h4(tail + TAIL, off), yt.h[i], yt.l[i],
+                                 f4{0.f, 0.f, 0.f, 0.f});
+    }
   }
 }
 
 // acc^T[16 dt + 4 g + j][row of the lane] += sum over the 32 block rows of X[row'][dim] w[row'], X from the
 // voff image pair at img, w (8 values of the lane's row, block rows 16 (e >> 2) + 4 g + (e & 3)) split to fp16
-QVIT_DEV void accum_t(const int8_t* img, const int (&voffs)[4], const float (&w)[8], f4 (&acc)[4]) {
+// (head dim 80: the fifth slice, dims 64 .. 79, from the tail image pair at tail)
+template <int D>
+QVIT_DEV void accum_t(const int8_t* img, const int8_t* tail, const int (&voffs)[4], const float (&w)[8],
+                      f4 (&acc)[D / 16]) {
   h8 wh, wl;
   split8(w, wh, wl);
 #pragma unroll
@@ -179,16 +221,29 @@ QVIT_DEV void accum_t(const int8_t* img, const int (&voffs)[4], const float (&w)
     const h8 xl = join(tr_read(img + IMG, voffs[dt]), tr_read(img + IMG, voffs[dt] + 16 * 128));
     acc[dt] = mfma3(xh, xl, wh, wl, acc[dt]);
   }
+  if constexpr (D == HD80) {
+    const int lane = threadIdx.x & 63;
+    const int off = vtoff(lane & 15, lane >> 4);
+    const h8 xh = join(tr_read(tail, off), tr_read(tail, off + 16 * 32));
+    const h8 xl = join(tr_read(tail + TAIL, off), tr_read(tail + TAIL, off + 16 * 32));
+    acc[4] = mfma3(xh, xl, wh, wl, acc[4]);
+  }
 }
 
 // ---- 2. query owner: row statistics, then dq ------------------------------------------------------------
 // LDS stage (24 KiB, double-buffered): K koff hi/lo, V koff hi/lo, K voff hi/lo.
-constexpr int QSTAGE = 6 * IMG;
+// Head dim 80: + the tail image pairs of K and V (4 KiB; K's serves the koff and the voff reads): 28 KiB.
+template <int D>
+constexpr int QSTAGE_OF = 6 * IMG + (D == HD80 ? 4 * TAIL : 0);
 
+// NT: owner tiles per wave (the workgroup owns NWAVES * NT * 16 queries)
+template <int D = HD, int NT = TW>
 __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(const float* __restrict__ qkv, const float* __restrict__ gout,
                                                         int N, int H, int64_t ldq, int64_t ldgo, float scale,
                                                         float in_scale, float g_scale, float* __restrict__ gqkv,
                                                         int64_t ldg, float* __restrict__ ws, int BH) {
+  constexpr int QSTAGE = QSTAGE_OF<D>;
+  constexpr int OGN = NWAVES * NT * 16;
   __shared__ __attribute__((aligned(16))) int8_t smem[2 * QSTAGE];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -196,41 +251,50 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(const float* __restrict_
   const int fr = lane & 15;
   const int g = lane >> 4;
 
-  const int ngroups = (N + OG - 1) / OG;
+  const int ngroups = (N + OGN - 1) / OGN;
   const int grp = blockIdx.x % ngroups;
   const int bh = blockIdx.x / ngroups;
   const int h = bh % H, b = bh / H;
-  const int C = H * HD;
+  const int C = H * D;
   const int64_t Np = np_of(N);
   const float* base = qkv + (int64_t)b * N * ldq;
-  const float* qcol = base + h * HD;
-  const float* kcol = base + C + h * HD;
-  const float* vcol = base + 2 * C + h * HD;
-  const float* gcol = gout + (int64_t)b * N * ldgo + h * HD;
+  const float* qcol = base + h * D;
+  const float* kcol = base + C + h * D;
+  const float* vcol = base + 2 * C + h * D;
+  const float* gcol = gout + (int64_t)b * N * ldgo + h * D;
   float* lse_w = ws + hdr_of(BH) + (int64_t)bh * Np;
   const float* D_w = ws + hdr_of(BH) + ((int64_t)BH + bh) * Np;
   const float rr = ds_scale(ws[bh]);
 
-  const int q0 = grp * OG;
-  h8 qh[TW][2], ql[TW][2], dh[TW][2], dl[TW][2];
-  bool tv[TW];
-  float Dq[TW];
+  const int q0 = grp * OGN;
+  h8 qh[NT][2], ql[NT][2], dh[NT][2], dl[NT][2];
+  [[maybe_unused]] TailFrag<NT, D> qt, dt_;   // columns 64 .. 79 of q and dO (head dim 80)
+  bool tv[NT];
+  float Dq[NT];
 #pragma unroll
-  for (int i = 0; i < TW; ++i) {
+  for (int i = 0; i < NT; ++i) {
     const int tile = wave + NWAVES * i;
     tv[i] = q0 + 16 * tile < N;  // wave-uniform
     int q = q0 + 16 * tile + fr;
     q = q < N ? q : N - 1;       // padded queries read a valid row; never stored
-    load_own(qcol, ldq, q, in_scale, qh[i], ql[i]);
-    load_own(gcol, ldgo, q, g_scale, dh[i], dl[i]);
+    load_own<D>(qcol, ldq, q, in_scale, qh[i], ql[i], qt, i);
+    load_own<D>(gcol, ldgo, q, g_scale, dh[i], dl[i], dt_, i);
     Dq[i] = D_w[q];
   }
 
   const int srow = tid >> 3, schunk = tid & 7;
   Chunk pk, pv;
+  [[maybe_unused]] f4 tk, tvv;                    // head dim 80: the tails' staging (load_tail)
+  [[maybe_unused]] const bool stail = tid < 128;  // wave-uniform (waves 0 and 1)
   auto load_block = [&](int kb, bool full) {
     pk = load_chunk(kcol, ldq, kb * KB + srow, N, schunk);
     if (full) pv = load_chunk(vcol, ldq, kb * KB + srow, N, schunk);
+    if constexpr (D == HD80) {
+      if (stail) {
+        tk = load_tail(kcol, ldq, kb * KB + (tid >> 2), N);
+        if (full) tvv = load_tail(vcol, ldq, kb * KB + (tid >> 2), N);
+      }
+    }
   };
   auto store_block = [&](int buf, bool full) {
     int8_t* st = smem + buf * QSTAGE;
@@ -242,6 +306,12 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(const float* __restrict_
       split_chunk(pv, in_scale, hi, lo);
       put(st + 2 * IMG, koff(srow, schunk), hi, lo);
     }
+    if constexpr (D == HD80) {
+      if (stail) {
+        put_tail(st + 6 * IMG, tk, in_scale);
+        if (full) put_tail(st + 6 * IMG + 2 * TAIL, tvv, in_scale);
+      }
+    }
   };
 
   int koffs[2][2], voffs[4];
@@ -250,9 +320,9 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(const float* __restrict_
   const int nkb = (N + KB - 1) / KB;
 
   // sweep 1: running max / sum of the scaled scores (log2 units), per lane over its 8 keys of each block
-  float m[TW], l[TW];
+  float m[NT], l[NT];
 #pragma unroll
-  for (int i = 0; i < TW; ++i) { m[i] = -INFINITY; l[i] = 0.f; }
+  for (int i = 0; i < NT; ++i) { m[i] = -INFINITY; l[i] = 0.f; }
   load_block(0, false);
   store_block(0, false);
   __syncthreads();
@@ -261,10 +331,10 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(const float* __restrict_
     const int8_t* st = smem + (kb & 1) * QSTAGE;
     const int kbase = kb * KB + 4 * g;
 #pragma unroll
-    for (int i = 0; i < TW; ++i) {
+    for (int i = 0; i < NT; ++i) {
       if (!tv[i]) continue;  // wave-uniform
       f4 s[2];
-      rows_dot(st, koffs, qh[i], ql[i], s);
+      rows_dot<D>(st, st + 6 * IMG, koffs, qh[i], ql[i], qt, i, s);
       float r[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) r[e] = (kbase + 16 * (e >> 2) + (e & 3) < N) ? s[e >> 2][e & 3] : -INFINITY;
@@ -282,20 +352,20 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(const float* __restrict_
     }
     __syncthreads();
   }
-  float lse[TW];
+  float lse[NT];
 #pragma unroll
-  for (int i = 0; i < TW; ++i) {
+  for (int i = 0; i < NT; ++i) {
     lse[i] = m[i] + __builtin_amdgcn_logf(xsum(l[i]));  // log2
     const int q = q0 + 16 * (wave + NWAVES * i) + fr;
     if (tv[i] && g == 0 && q < N) lse_w[q] = lse[i];
   }
 
   // sweep 2: dq^T += K^T . dS'^T
-  f4 acc[TW][4];
+  f4 acc[NT][D / 16];
 #pragma unroll
-  for (int i = 0; i < TW; ++i)
+  for (int i = 0; i < NT; ++i)
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) acc[i][dt] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < D / 16; ++dt) acc[i][dt] = f4{0.f, 0.f, 0.f, 0.f};
   load_block(0, true);
   store_block(0, true);
   __syncthreads();
@@ -304,11 +374,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(const float* __restrict_
     const int8_t* st = smem + (kb & 1) * QSTAGE;
     const int kbase = kb * KB + 4 * g;
 #pragma unroll
-    for (int i = 0; i < TW; ++i) {
+    for (int i = 0; i < NT; ++i) {
       if (!tv[i]) continue;  // wave-uniform
       f4 s[2], dp[2];
-      rows_dot(st, koffs, qh[i], ql[i], s);
-      rows_dot(st + 2 * IMG, koffs, dh[i], dl[i], dp);
+      rows_dot<D>(st, st + 6 * IMG, koffs, qh[i], ql[i], qt, i, s);
+      rows_dot<D>(st + 2 * IMG, st + 6 * IMG + 2 * TAIL, koffs, dh[i], dl[i], dt_, i, dp);
       float w[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -316,7 +386,7 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(const float* __restrict_
         const float p = __builtin_amdgcn_exp2f(fmaf(s[e >> 2][e & 3], sl2, -lse[i]));
         w[e] = ok ? p * ((dp[e >> 2][e & 3] - Dq[i]) * rr) : 0.f;   // |w| < 2^15 (ds_scale)
       }
-      accum_t(st + 4 * IMG, voffs, w, acc[i]);
+      accum_t<D>(st + 4 * IMG, st + 6 * IMG, voffs, w, acc[i]);
     }
     if (kb + 1 < nkb) {
       __syncthreads();
@@ -327,24 +397,30 @@ __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(const float* __restrict_
   // acc = g_scale in_scale^2 r sum_j dS_ij k_j
   const float cq = scale / (g_scale * in_scale * in_scale * rr);
 #pragma unroll
-  for (int i = 0; i < TW; ++i) {
+  for (int i = 0; i < NT; ++i) {
     const int q = q0 + 16 * (wave + NWAVES * i) + fr;
     if (!tv[i] || q >= N) continue;
-    float* dst = gqkv + ((int64_t)b * N + q) * ldg + h * HD + 4 * g;
+    float* dst = gqkv + ((int64_t)b * N + q) * ldg + h * D + 4 * g;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) *reinterpret_cast<f4*>(dst + 16 * dt) = acc[i][dt] * cq;
+    for (int dt = 0; dt < D / 16; ++dt) *reinterpret_cast<f4*>(dst + 16 * dt) = acc[i][dt] * cq;
   }
 }
 
 // ---- 3. key owner: dk, dv ----------------------------------------------------------------------------------
 // LDS stage (32 KiB, double-buffered): Q koff hi/lo, dO koff hi/lo, Q voff hi/lo, dO voff hi/lo.
-constexpr int KSTAGE = 8 * IMG;
+// Head dim 80: + the tail image pairs of Q and dO (4 KiB; each serves its koff and its voff reads): 36 KiB, 72 KiB
+// per workgroup (a gfx950 workgroup may take up to 160 KiB), two workgroups per CU.
+template <int D>
+constexpr int KSTAGE_OF = 8 * IMG + (D == HD80 ? 4 * TAIL : 0);
 
+template <int D = HD, int NT = TW>
 __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const float* __restrict__ qkv,
                                                          const float* __restrict__ gout, int N, int H, int64_t ldq,
                                                          int64_t ldgo, float scale, float in_scale, float g_scale,
                                                          float* __restrict__ gqkv, int64_t ldg,
                                                          const float* __restrict__ ws, int BH) {
+  constexpr int KSTAGE = KSTAGE_OF<D>;
+  constexpr int OGN = NWAVES * NT * 16;
   __shared__ __attribute__((aligned(16))) int8_t smem[2 * KSTAGE];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -352,40 +428,49 @@ __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const float* __restrict
   const int fr = lane & 15;
   const int g = lane >> 4;
 
-  const int ngroups = (N + OG - 1) / OG;
+  const int ngroups = (N + OGN - 1) / OGN;
   const int grp = blockIdx.x % ngroups;
   const int bh = blockIdx.x / ngroups;
   const int h = bh % H, b = bh / H;
-  const int C = H * HD;
+  const int C = H * D;
   const int64_t Np = np_of(N);
   const float* base = qkv + (int64_t)b * N * ldq;
-  const float* qcol = base + h * HD;
-  const float* kcol = base + C + h * HD;
-  const float* vcol = base + 2 * C + h * HD;
-  const float* gcol = gout + (int64_t)b * N * ldgo + h * HD;
+  const float* qcol = base + h * D;
+  const float* kcol = base + C + h * D;
+  const float* vcol = base + 2 * C + h * D;
+  const float* gcol = gout + (int64_t)b * N * ldgo + h * D;
   const float* lse_w = ws + hdr_of(BH) + (int64_t)bh * Np;
   const float* D_w = ws + hdr_of(BH) + ((int64_t)BH + bh) * Np;
   const float rr = ds_scale(ws[bh]);
   const float rp = rr * (1.f / (float)(1 << P_SHIFT));   // dS' = (2^14 P) ((dP' - D') r 2^-14)
 
-  const int k0 = grp * OG;
-  h8 kh[TW][2], kl[TW][2], vh[TW][2], vl[TW][2];
-  bool tv[TW];
+  const int k0 = grp * OGN;
+  h8 kh[NT][2], kl[NT][2], vh[NT][2], vl[NT][2];
+  [[maybe_unused]] TailFrag<NT, D> kt_, vt_;   // columns 64 .. 79 of k and v (head dim 80)
+  bool tv[NT];
 #pragma unroll
-  for (int i = 0; i < TW; ++i) {
+  for (int i = 0; i < NT; ++i) {
     const int tile = wave + NWAVES * i;
     tv[i] = k0 + 16 * tile < N;  // wave-uniform
     int key = k0 + 16 * tile + fr;
     key = key < N ? key : N - 1;  // padded keys read a valid row; never stored
-    load_own(kcol, ldq, key, in_scale, kh[i], kl[i]);
-    load_own(vcol, ldq, key, in_scale, vh[i], vl[i]);
+    load_own<D>(kcol, ldq, key, in_scale, kh[i], kl[i], kt_, i);
+    load_own<D>(vcol, ldq, key, in_scale, vh[i], vl[i], vt_, i);
   }
 
   const int srow = tid >> 3, schunk = tid & 7;
   Chunk pq, pg;
+  [[maybe_unused]] f4 tq, tg;                     // head dim 80: the tails' staging (load_tail)
+  [[maybe_unused]] const bool stail = tid < 128;  // wave-uniform (waves 0 and 1)
   auto load_block = [&](int qb) {
     pq = load_chunk(qcol, ldq, qb * KB + srow, N, schunk);
     pg = load_chunk(gcol, ldgo, qb * KB + srow, N, schunk);
+    if constexpr (D == HD80) {
+      if (stail) {
+        tq = load_tail(qcol, ldq, qb * KB + (tid >> 2), N);
+        tg = load_tail(gcol, ldgo, qb * KB + (tid >> 2), N);
+      }
+    }
   };
   auto store_block = [&](int buf) {
     int8_t* st = smem + buf * KSTAGE;
@@ -396,6 +481,12 @@ __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const float* __restrict
     split_chunk(pg, g_scale, hi, lo);
     put(st + 2 * IMG, koff(srow, schunk), hi, lo);
     put(st + 6 * IMG, voff(srow, 16 * schunk), hi, lo);
+    if constexpr (D == HD80) {
+      if (stail) {
+        put_tail(st + 8 * IMG, tq, in_scale);
+        put_tail(st + 8 * IMG + 2 * TAIL, tg, g_scale);
+      }
+    }
   };
 
   int koffs[2][2], voffs[4];
@@ -403,11 +494,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const float* __restrict
   const float sl2 = scale * LOG2E / (in_scale * in_scale);
   const int nqb = (N + KB - 1) / KB;
 
-  f4 dk[TW][4], dv[TW][4];
+  f4 dk[NT][D / 16], dv[NT][D / 16];
 #pragma unroll
-  for (int i = 0; i < TW; ++i)
+  for (int i = 0; i < NT; ++i)
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) dk[i][dt] = dv[i][dt] = f4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < D / 16; ++dt) dk[i][dt] = dv[i][dt] = f4{0.f, 0.f, 0.f, 0.f};
 
   load_block(0);
   store_block(0);
@@ -427,11 +518,11 @@ __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const float* __restrict
       for (int j = 0; j < 4; ++j) { nl[4 * t + j] = (float)P_SHIFT - a[j]; Dq[4 * t + j] = d[j]; }
     }
 #pragma unroll
-    for (int i = 0; i < TW; ++i) {
+    for (int i = 0; i < NT; ++i) {
       if (!tv[i]) continue;  // wave-uniform
       f4 s[2], dp[2];
-      rows_dot(st, koffs, kh[i], kl[i], s);
-      rows_dot(st + 2 * IMG, koffs, vh[i], vl[i], dp);
+      rows_dot<D>(st, st + 8 * IMG, koffs, kh[i], kl[i], kt_, i, s);
+      rows_dot<D>(st + 2 * IMG, st + 8 * IMG + 2 * TAIL, koffs, vh[i], vl[i], vt_, i, dp);
       float p[8], w[8];
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -440,8 +531,8 @@ __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const float* __restrict
         p[e] = ok ? pe : 0.f;
         w[e] = ok ? pe * ((dp[e >> 2][e & 3] - Dq[e]) * rp) : 0.f;                     // |w| < 2^15 (ds_scale)
       }
-      accum_t(st + 6 * IMG, voffs, p, dv[i]);
-      accum_t(st + 4 * IMG, voffs, w, dk[i]);
+      accum_t<D>(st + 6 * IMG, st + 8 * IMG + 2 * TAIL, voffs, p, dv[i]);
+      accum_t<D>(st + 4 * IMG, st + 8 * IMG, voffs, w, dk[i]);
     }
     if (qb + 1 < nqb) {
       __syncthreads();
@@ -453,12 +544,12 @@ __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const float* __restrict
   const float ck = scale / (g_scale * in_scale * in_scale * rr);
   const float cv = 1.f / (g_scale * (float)(1 << P_SHIFT));
 #pragma unroll
-  for (int i = 0; i < TW; ++i) {
+  for (int i = 0; i < NT; ++i) {
     const int key = k0 + 16 * (wave + NWAVES * i) + fr;
     if (!tv[i] || key >= N) continue;
-    float* dst = gqkv + ((int64_t)b * N + key) * ldg + h * HD + 4 * g;
+    float* dst = gqkv + ((int64_t)b * N + key) * ldg + h * D + 4 * g;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) {
+    for (int dt = 0; dt < D / 16; ++dt) {
       *reinterpret_cast<f4*>(dst + C + 16 * dt) = dk[i][dt] * ck;
       *reinterpret_cast<f4*>(dst + 2 * C + 16 * dt) = dv[i][dt] * cv;
     }
@@ -477,8 +568,9 @@ extern "C" int qvit_attention_backward(const float* qkv, const float* out, const
                                        int64_t ldgo, float scale, float in_scale, float g_scale, float* grad_qkv,
                                        int64_t ldg, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   if (!qkv || !out || !grad_out || !grad_qkv) return QVIT_ENULL;
-  if (head_dim != HD) return QVIT_EINVAL;
-  if (B < 0 || N <= 0 || H <= 0 || ldq < 3 * H * HD || ldg < 3 * H * HD || ldo < H * HD || ldgo < H * HD)
+  if (head_dim != HD && head_dim != HD80) return QVIT_EINVAL;
+  if (B < 0 || N <= 0 || H <= 0 || ldq < 3 * H * head_dim || ldg < 3 * H * head_dim || ldo < H * head_dim ||
+      ldgo < H * head_dim)
     return QVIT_EINVAL;
   if (B * N > INT32_MAX || N > (1 << 20) || !(in_scale > 0.f) || !(g_scale > 0.f)) return QVIT_EINVAL;
   if ((ldq % 4) || (ldo % 4) || (ldgo % 4) || (ldg % 4)) return QVIT_EALIGN;
@@ -495,11 +587,23 @@ extern "C" int qvit_attention_backward(const float* qkv, const float* out, const
   const int64_t nblk = BH * ((N + OG - 1) / OG);
   if (nblk > INT32_MAX) return QVIT_EINVAL;
   float* ws = reinterpret_cast<float*>(workspace);
-  hipLaunchKernelGGL(bwd_prep_kernel, dim3((unsigned)BH), dim3(256), 0, stream, qkv, out, grad_out, (int)N, (int)H,
-                     ldq, ldo, ldgo, in_scale, g_scale, ws);
-  hipLaunchKernelGGL(bwd_dq_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, qkv, grad_out, (int)N, (int)H, ldq,
-                     ldgo, scale, in_scale, g_scale, grad_qkv, ldg, ws, (int)BH);
-  hipLaunchKernelGGL(bwd_dkv_kernel, dim3((unsigned)nblk), dim3(256), 0, stream, qkv, grad_out, (int)N, (int)H, ldq,
-                     ldgo, scale, in_scale, g_scale, grad_qkv, ldg, ws, (int)BH);
+  if (head_dim == HD80) {
+    hipLaunchKernelGGL(bwd_prep_kernel<HD80>, dim3((unsigned)BH), dim3(256), 0, stream, qkv, out, grad_out, (int)N,
+                       (int)H, ldq, ldo, ldgo, in_scale, g_scale, ws);
+    constexpr int OGQ = NWAVES * TWQ80 * 16, OGK = NWAVES * TWK80 * 16;
+    const int64_t nblk_q = BH * ((N + OGQ - 1) / OGQ), nblk_k = BH * ((N + OGK - 1) / OGK);
+    if (nblk_k > INT32_MAX) return QVIT_EINVAL;
+    hipLaunchKernelGGL((bwd_dq_kernel<HD80, TWQ80>), dim3((unsigned)nblk_q), dim3(256), 0, stream, qkv, grad_out,
+                       (int)N, (int)H, ldq, ldgo, scale, in_scale, g_scale, grad_qkv, ldg, ws, (int)BH);
+    hipLaunchKernelGGL((bwd_dkv_kernel<HD80, TWK80>), dim3((unsigned)nblk_k), dim3(256), 0, stream, qkv, grad_out,
+                       (int)N, (int)H, ldq, ldgo, scale, in_scale, g_scale, grad_qkv, ldg, ws, (int)BH);
+    return qvit_hip_status(hipGetLastError());
+  }
+  hipLaunchKernelGGL(bwd_prep_kernel<HD>, dim3((unsigned)BH), dim3(256), 0, stream, qkv, out, grad_out, (int)N,
+                     (int)H, ldq, ldo, ldgo, in_scale, g_scale, ws);
+  hipLaunchKernelGGL((bwd_dq_kernel<HD, TW>), dim3((unsigned)nblk), dim3(256), 0, stream, qkv, grad_out, (int)N,
+                     (int)H, ldq, ldgo, scale, in_scale, g_scale, grad_qkv, ldg, ws, (int)BH);
+  hipLaunchKernelGGL((bwd_dkv_kernel<HD, TW>), dim3((unsigned)nblk), dim3(256), 0, stream, qkv, grad_out, (int)N,
+                     (int)H, ldq, ldgo, scale, in_scale, g_scale, grad_qkv, ldg, ws, (int)BH);
   return qvit_hip_status(hipGetLastError());
 }

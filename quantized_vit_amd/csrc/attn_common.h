@@ -7,14 +7,40 @@
 namespace qvit_attn {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef short s8v __attribute__((ext_vector_type(8)));
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 
-constexpr int HD = 64;          // head dim (the only one supported)
+constexpr int HD = 64;          // head dim of the fused and split kernels; the first 64 columns of a wider head
+constexpr int HD80 = 80;        // the other head dim of attn_kernel (fp32 output) and the backward kernels (ViT-Huge/14)
 constexpr int KB = 32;          // keys per block
 constexpr int IMG = KB * HD * 2;       // one fp16 image of a key block: 4 KiB
+// Head dim 80 = 64 + 16. A key block's image keeps its first 64 columns in the 128-B-row image above, same
+// swizzles, and puts columns 64 .. 79 in a tail image of 32-B rows, not swizzled (row r, column 64 + j at
+// 32 r + 2 j): 160 B per row in all, nothing padded. Both kinds of read take 8 B per lane from it:
+//   q . k  : lane (fr, g) reads row 16 kt + fr, columns 64 + 4 g .. + 3 (the A operand of one K = 16 MFMA step):
+//            a wave covers 16 rows x 32 B = 512 contiguous bytes;
+//   V^T    : lane (fr, g) reads row 4 g + (fr >> 2), columns 64 + 4 (fr & 3) .. + 3 (ds_read_b64_tr_b16, the fifth
+//            16-dim slice): again 512 contiguous bytes per wave.
+// 512 contiguous bytes are two full 64-bank rows, so both reads, and the staging's 8-B writes (thread t: row
+// t >> 2, part t & 3: contiguous as well), are conflict-free. One tail therefore serves as "koff" and as "voff"
+// image in the backward kernels. Nothing depends on that for correctness: the offsets below are the whole contract.
+constexpr int TAIL = KB * 32;          // one fp16 tail image of a key block: 1 KiB
+QVIT_DEV int ktoff(int r, int g) { return r * 32 + 8 * g; }
+QVIT_DEV int vtoff(int fr, int g) { return (4 * g + (fr >> 2)) * 32 + 8 * (fr & 3); }
+// The q . k contraction over 80 columns is two K = 32 steps and one K = 16 step (v_mfma_f32_16x16x16_f16), not
+// three K = 32 steps on images padded to 96: the padded form costs 4 more registers per query tile and operand
+// half (24 at 3 tiles per wave), 25 % more LDS and reads, and a third of its last step multiplies zeros; the K = 16
+// step has the same lane layout (lane (fr, g): row fr, k = 4 g .. 4 g + 3) with 4 values instead of 8.
+// The queries' columns 64 .. 79 as that step's B operand, per tile (empty at head dim 64):
+template <int T, int D>
+struct TailFrag {};
+template <int T>
+struct TailFrag<T, HD80> {
+  h4 h[T], l[T];
+};
 constexpr float LOG2E = 1.4426950408889634f;
 
 QVIT_DEV int koff(int r, int c) { return r * 128 + 16 * (c ^ ((r >> 1) & 7)); }
@@ -23,6 +49,15 @@ QVIT_DEV int voff(int r, int byte) { return r * 128 + 32 * ((byte >> 5) ^ ((r >>
 QVIT_DEV void split8(const float (&x)[8], h8& hi, h8& lo) {
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
+    const _Float16 h = (_Float16)x[i];
+    hi[i] = h;
+    lo[i] = (_Float16)(x[i] - (float)h);
+  }
+}
+
+QVIT_DEV void split4(f4 x, h4& hi, h4& lo) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
     const _Float16 h = (_Float16)x[i];
     hi[i] = h;
     lo[i] = (_Float16)(x[i] - (float)h);
@@ -57,6 +92,8 @@ QVIT_DEV void split8_mix(const float (&x)[8], h8& hi, h8& lo) {
 
 QVIT_DEV h8 lds_h8(const int8_t* base, int off) { return *reinterpret_cast<const h8*>(base + off); }
 
+QVIT_DEV h4 lds_h4(const int8_t* base, int off) { return *reinterpret_cast<const h4*>(base + off); }
+
 QVIT_DEV s4v tr_read(const int8_t* base, int off) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s4v*)(uintptr_t)(const __attribute__((address_space(3))) void*)(base + off));
@@ -71,6 +108,17 @@ QVIT_DEV f4 mfma3(h8 ah, h8 al, h8 bh, h8 bl, f4 c) {
   c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bh, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah, bl, c, 0, 0, 0);
   c = __builtin_amdgcn_mfma_f32_16x16x32_f16(al, bh, c, 0, 0, 0);
+  return c;
+}
+
+// the K = 16 step of a head-dim-80 q . k contraction (columns 64 .. 79). Callers pass c = 0 and add the result on
+// the VALU, so the two MFMA shapes never depend on each other. Observed on the MI355X, cause not isolated: with
+// the fresh result of a K = 32 MFMA as this instruction's SrcC a few cycles later, the backward kernels' sums were
+// wrong and varied from run to run (missing hazard wait states suspected). Not a documented hardware rule.
+QVIT_DEV f4 mfma3t(h4 ah, h4 al, h4 bh, h4 bl, f4 c) {
+  c = __builtin_amdgcn_mfma_f32_16x16x16f16(ah, bh, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x16f16(ah, bl, c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_16x16x16f16(al, bh, c, 0, 0, 0);
   return c;
 }
 
@@ -103,11 +151,16 @@ QVIT_DEV float xsum(float v) {
 // s[i][kt][j] = S^T[key kbase + 16 kt + j][query of the lane]; scores in log2 units (sl2).
 // MASK: the block holds keys >= N (the last block only).
 // T: query tiles per wave (arrays); IMGS: byte distance between the K hi, K lo, V hi and V lo images.
-template <int T, int IMGS = IMG, bool VEARLY = false>
+// D: head dim. At 80 the four tail images (K hi, K lo, V hi, V lo; TAIL bytes each) follow the four images at
+// st + 4 IMGS, qt holds the queries' columns 64 .. 79, and o has a fifth 16-dim slice.
+template <int T, int IMGS = IMG, bool VEARLY = false, int D = HD>
 QVIT_DEV void attend(int nt, bool mask, const int8_t* st, const h8 (&qh)[T][2], const h8 (&ql)[T][2], float (&m)[T],
-                     float (&l)[T], f4 (&o)[T][4], const int (&koffs)[2][2], const int (&voffs)[4], int kbase,
-                     int N, float sl2, Stamps& sp) {
+                     float (&l)[T], f4 (&o)[T][D / 16], const int (&koffs)[2][2], const int (&voffs)[4], int kbase,
+                     int N, float sl2, Stamps& sp, const TailFrag<T, D>& qt = {}) {
   constexpr int NT = T;
+  constexpr int ND = D / 16;
+  static_assert(D == HD || (D == HD80 && !VEARLY), "head dim 64 or 80");
+  [[maybe_unused]] const int8_t* tail = st + 4 * IMGS;
   f4 s[NT][2];
   // the last block's second 16 keys all past N (N % 32 in 1..16): their scores are masked, skip them
   const bool half = mask && (kbase & ~31) + 16 >= N;  // kbase = block start + 4 g, g < 4
@@ -131,6 +184,18 @@ QVIT_DEV void attend(int nt, bool mask, const int8_t* st, const h8 (&qh)[T][2], 
 #pragma unroll
         for (int c = 0; c < 2; ++c) s[i][kt] = mfma3(kh[kt][c], kl[kt][c], qh[i][c], ql[i][c], s[i][kt]);
       }
+    if constexpr (D == HD80) {
+      const int lane = threadIdx.x & 63;
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt) {
+        if (kt == 1 && half) continue;
+        const int off = ktoff(16 * kt + (lane & 15), lane >> 4);
+        const h4 th = lds_h4(tail, off), tl = lds_h4(tail + TAIL, off);
+#pragma unroll
+        for (int i = 0; i < NT; ++i)
+          if (i < nt) s[i][kt] = s[i][kt] + mfma3t(th, tl, qt.h[i], qt.l[i], f4{0.f, 0.f, 0.f, 0.f});
+      }
+    }
   }
   sp.mark(1);
   // VEARLY: the V fragments of the whole block are issued before the softmax and land while it runs, so
@@ -168,7 +233,7 @@ QVIT_DEV void attend(int nt, bool mask, const int8_t* st, const h8 (&qh)[T][2], 
       const float alpha = __builtin_amdgcn_exp2f(m[i] - mn);
       l[i] *= alpha;
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) o[i][dt] = o[i][dt] * alpha;
+      for (int dt = 0; dt < ND; ++dt) o[i][dt] = o[i][dt] * alpha;
       m[i] = mn;
     }
     const float nm = -m[i];
@@ -191,6 +256,15 @@ QVIT_DEV void attend(int nt, bool mask, const int8_t* st, const h8 (&qh)[T][2], 
 #pragma unroll
     for (int i = 0; i < NT; ++i)
       if (i < nt) o[i][dt] = mfma3(vh[dt], vl[dt], ph[i], pl[i], o[i][dt]);
+  }
+  if constexpr (D == HD80) {  // dims 64 .. 79 from the V tails
+    const int lane = threadIdx.x & 63;
+    const int off = vtoff(lane & 15, lane >> 4);
+    const h8 th = join(tr_read(tail + 2 * TAIL, off), tr_read(tail + 2 * TAIL, off + 16 * 32));
+    const h8 tl = join(tr_read(tail + 3 * TAIL, off), tr_read(tail + 3 * TAIL, off + 16 * 32));
+#pragma unroll
+    for (int i = 0; i < NT; ++i)
+      if (i < nt) o[i][4] = mfma3(th, tl, ph[i], pl[i], o[i][4]);
   }
   sp.mark(3);
 }
@@ -215,12 +289,13 @@ QVIT_DEV void transpose_groups(uint32_t (&w)[4]) {
 // Normalise and write a wave's query tiles: fp32 rows, or the next layer's int8 codes. With st16 the
 // codes of a row leave as one 16-B store per lane (lane group g: columns 16g .. 16g+15 of the head).
 // Tile i of the wave is query tile qtile0 + tstride * i of the group starting at q0.
-template <int OUT, int T>
-QVIT_DEV void attend_store(const bool (&tv)[T], const float (&l)[T], const f4 (&o)[T][4], int qtile0, int tstride,
+template <int OUT, int T, int D = HD>
+QVIT_DEV void attend_store(const bool (&tv)[T], const float (&l)[T], const f4 (&o)[T][D / 16], int qtile0, int tstride,
                            int q0, int N, int b, int h, float in_scale, void* out, int64_t ldo, const QParams& qp,
                            const EpiLds& tb, bool st16) {
   const int lane = threadIdx.x & 63;
   const int fr = lane & 15, g = lane >> 4;
+  static_assert(D == HD || (D == HD80 && OUT == 0), "the int8 epilogue is for head dim 64");
 #pragma unroll
   for (int i = 0; i < T; ++i) {
     if (!tv[i]) continue;  // wave-uniform
@@ -230,8 +305,8 @@ QVIT_DEV void attend_store(const bool (&tv)[T], const float (&l)[T], const f4 (&
     if (OUT == 0) {
       if (q >= N) continue;
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
-        const int col = h * HD + 16 * dt + 4 * g;
+      for (int dt = 0; dt < D / 16; ++dt) {
+        const int col = h * D + 16 * dt + 4 * g;
         *reinterpret_cast<f4*>(reinterpret_cast<float*>(out) + row * ldo + col) = o[i][dt] * inv;
       }
       continue;

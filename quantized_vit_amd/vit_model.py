@@ -148,12 +148,15 @@ def _pow2_grad_scale(gmax: float) -> float:
     return 2.0 ** max(-100, min(100, 14 - math.ceil(math.log2(gmax))))
 
 
-def _attention_core_forward(q2: torch.Tensor, B: int, N: int, H: int, scale: float):
-    """qvit_attention (fp32 out) on the [B*N, 3*H*64] qkv projection. Returns (out, in_scale)."""
-    out = torch.empty((B * N, H * 64), dtype=torch.float32, device=q2.device)
+HIP_HEAD_DIMS = (64, 80)   # head sizes of qvit_attention (fp32 output) and qvit_attention_backward
+
+
+def _attention_core_forward(q2: torch.Tensor, B: int, N: int, H: int, scale: float, hd: int):
+    """qvit_attention (fp32 out) on the [B*N, 3*H*hd] qkv projection. Returns (out, in_scale)."""
+    out = torch.empty((B * N, H * hd), dtype=torch.float32, device=q2.device)
     amax = float(q2.abs().max()) if q2.numel() else 0.0   # unfused path: no plan bound, one sync
     in_scale = _pow2_scale(amax)
-    _lib.attention(q2, B, N, H, 64, scale, out, _lib.ATT_F32, in_scale)
+    _lib.attention(q2, B, N, H, hd, scale, out, _lib.ATT_F32, in_scale)
     return out, in_scale
 
 
@@ -162,29 +165,29 @@ class _AttentionCore(torch.autograd.Function):
     backward one qvit_attention_backward. Saves qkv and the output only: nothing of size N x N."""
 
     @staticmethod
-    def forward(ctx, q2, B, N, H, scale):
+    def forward(ctx, q2, B, N, H, scale, hd):
         q2 = q2.detach()
         if q2.stride(1) != 1 or q2.stride(0) % 4 or q2.data_ptr() % 16:
             q2 = q2.contiguous()
-        out, in_scale = _attention_core_forward(q2, B, N, H, scale)
+        out, in_scale = _attention_core_forward(q2, B, N, H, scale, hd)
         ctx.save_for_backward(q2, out)
-        ctx.meta = (B, N, H, scale, in_scale)
+        ctx.meta = (B, N, H, scale, in_scale, hd)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         q2, out = ctx.saved_tensors
-        B, N, H, scale, in_scale = ctx.meta
+        B, N, H, scale, in_scale, hd = ctx.meta
         g = grad_out.detach()
         if g.dtype != torch.float32 or g.dim() != 2 or g.stride(1) != 1 or g.stride(0) % 4 or g.data_ptr() % 16:
             g = g.float().contiguous()
         gmax = float(g.abs().max()) if g.numel() else 0.0      # one sync, as in_scale in the forward
         g_scale = _pow2_grad_scale(gmax)
         dqkv = torch.empty((B * N, q2.shape[1]), dtype=torch.float32, device=q2.device)
-        if q2.shape[1] > 3 * H * 64:
-            dqkv[:, 3 * H * 64:] = 0
-        _lib.attention_backward(q2, out, g, B, N, H, 64, scale, in_scale, g_scale, dqkv)
-        return dqkv, None, None, None, None
+        if q2.shape[1] > 3 * H * hd:
+            dqkv[:, 3 * H * hd:] = 0
+        _lib.attention_backward(q2, out, g, B, N, H, hd, scale, in_scale, g_scale, dqkv)
+        return dqkv, None, None, None, None, None
 
 
 class ViTAttention(nn.Module):
@@ -202,7 +205,7 @@ class ViTAttention(nn.Module):
         self.proj_drop = nn.Dropout(proj_drop_ratio)
 
     def hip_ok(self, qkv: torch.Tensor) -> bool:
-        return (qkv.is_cuda and qkv.dtype == torch.float32 and self.head_dim == 64 and qkv.dim() == 2
+        return (qkv.is_cuda and qkv.dtype == torch.float32 and self.head_dim in HIP_HEAD_DIMS and qkv.dim() == 2
                 and qkv.stride(1) == 1 and not (self.training and self.attn_drop.p > 0))
 
     def split_ok(self, p_qkv) -> bool:
@@ -213,20 +216,20 @@ class ViTAttention(nn.Module):
     def core_hip(self, qkv: torch.Tensor, B: int, N: int, out: torch.Tensor, out_mode: int = _lib.ATT_F32,
                  in_scale: float = 1.0, plan=None) -> torch.Tensor:
         """The same op on the fused HIP kernel (qvit_attention); with out_mode ATT_I8 it also applies the
-        activation quantizer of `plan` (the proj layer) and writes its int8 codes."""
+        activation quantizer of `plan` (the proj layer) and writes its int8 codes (head_dim 64 only)."""
         if out_mode == _lib.ATT_I8:
-            return _lib.attention(qkv, B, N, self.num_heads, 64, self.scale, out, out_mode, in_scale, plan.qtype,
-                                  plan.d_act, plan.qm_act, plan.t_act)
-        return _lib.attention(qkv, B, N, self.num_heads, 64, self.scale, out, out_mode, in_scale)
+            return _lib.attention(qkv, B, N, self.num_heads, self.head_dim, self.scale, out, out_mode, in_scale,
+                                  plan.qtype, plan.d_act, plan.qm_act, plan.t_act)
+        return _lib.attention(qkv, B, N, self.num_heads, self.head_dim, self.scale, out, out_mode, in_scale)
 
     def core(self, qkv: torch.Tensor, B: int, N: int) -> torch.Tensor:
         """softmax(q k^T * scale) v on the qkv projection (vit_model.py:133-149), fp32."""
         if self.hip_ok(qkv.reshape(B * N, -1)):
             if torch.is_grad_enabled() and qkv.requires_grad:   # same kernel, with qvit_attention_backward behind it
-                return _AttentionCore.apply(qkv.reshape(B * N, -1), B, N, self.num_heads,
-                                            self.scale).reshape(B, N, -1)
-            return _attention_core_forward(qkv.reshape(B * N, -1), B, N, self.num_heads, self.scale)[0].reshape(
-                B, N, -1)
+                return _AttentionCore.apply(qkv.reshape(B * N, -1), B, N, self.num_heads, self.scale,
+                                            self.head_dim).reshape(B, N, -1)
+            return _attention_core_forward(qkv.reshape(B * N, -1), B, N, self.num_heads, self.scale,
+                                           self.head_dim)[0].reshape(B, N, -1)
         qkv = qkv.reshape(B, N, 3, self.num_heads, -1).permute(2, 0, 3, 1, 4)
         q, k, v = qkv[0], qkv[1], qkv[2]
         attn = (q @ k.transpose(-2, -1)) * self.scale
@@ -449,8 +452,9 @@ class Block(nn.Module):
         qkv = a.qkv.gemm_codes(codes, p_qkv, _lib.EPI_F32)
         if qkv.shape[1] != p_qkv.n:
             qkv = qkv[:, :p_qkv.n]
-        if a.hip_ok(qkv):
+        if a.hip_ok(qkv) and a.head_dim == 64:
             # attention core + proj's activation quantizer in one kernel: int8 codes for the proj GEMM
+            # (head_dim 80: the fp32 core below, then proj's quantizer on its own)
             codes = torch.empty((M, p_proj.kpad), dtype=torch.int8, device=x.device)
             if p_proj.kpad != a.num_heads * 64:
                 codes[:, a.num_heads * 64:].zero_()

@@ -1,5 +1,7 @@
 """Times qvit_attention on the ViT-B/16 b256 shape (B=256, N=197, H=12, hd=64) against torch's fp32
-bmm + softmax + bmm sequence on the same qkv, with HIP events (median over iters)."""
+bmm + softmax + bmm sequence on the same qkv, with HIP events (median over iters).
+--hd 80 (ViT-Huge/14: --B 64 --N 257 --H 16 --hd 80) times the fp32-output kernel against the torch ops, the two
+alternated in one process, with the peak allocation of each."""
 import argparse
 import os
 import sys
@@ -24,11 +26,44 @@ def timeit(fn, iters):
     return ms[len(ms) // 2]
 
 
+def head_dim_ab(dev, B, N, H, hd, iters):
+    """qvit_attention (fp32 out) against the torch ops at head dim hd: alternated rounds, the median of each route's
+    medians, and the peak allocation over one call of each (above what is allocated before the call)."""
+    qkv = torch.randn(B * N, 3 * H * hd, device=dev)
+    out = torch.empty(B * N, H * hd, device=dev)
+    scale = hd ** -0.5
+
+    def torch_ref():
+        x = qkv.reshape(B, N, 3, H, hd).permute(2, 0, 3, 1, 4)
+        at = ((x[0] @ x[1].transpose(-2, -1)) * scale).softmax(dim=-1)
+        return (at @ x[2]).transpose(1, 2).reshape(B * N, H * hd)
+
+    routes = {"qvit_attention f32": lambda: _lib.attention(qkv, B, N, H, hd, scale, out), "torch fp32": torch_ref}
+    times = {k: [] for k in routes}
+    for fn in routes.values():   # warm both routes before the first timed round
+        timeit(fn, iters)
+    for _ in range(3):
+        for k, fn in routes.items():
+            times[k].append(timeit(fn, iters))
+    flops = 4.0 * B * H * N * N * hd
+    for k, fn in routes.items():
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats(dev)
+        before = torch.cuda.memory_allocated(dev)
+        fn()
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated(dev) - before
+        ms = sorted(times[k])[1]
+        print(f"hd={hd} B={B} N={N} H={H} {k:20s} {ms*1e3:9.1f} us  {flops/ms/1e9:8.1f} TFLOP/s (fp32-equivalent)  "
+              f"peak +{peak / 2**20:8.1f} MiB  rounds {' '.join(f'{t*1e3:.1f}' for t in times[k])}", flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--B", type=int, default=256)
     ap.add_argument("--N", type=int, default=197)
     ap.add_argument("--H", type=int, default=12)
+    ap.add_argument("--hd", type=int, default=64, choices=(64, 80), help="head dim (80: fp32 output and torch only)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--lib", default="", help="load this library build instead (diagnostic variants)")
     ap.add_argument("--split-only", action="store_true")
@@ -40,6 +75,8 @@ def main():
         _lib.load(a.lib)
     dev = torch.device("cuda:0")
     B, N, H = a.B, a.N, a.H
+    if a.hd != 64:
+        return head_dim_ab(dev, B, N, H, a.hd, a.iters)
     qkv = torch.randn(B * N, 3 * H * 64, device=dev)
     out = torch.empty(B * N, H * 64, device=dev)
     codes = torch.empty(B * N, H * 64, dtype=torch.int8, device=dev)

@@ -1,7 +1,8 @@
 """ViTAttention.core forward + backward: the HIP path (qvit_attention + qvit_attention_backward behind
 _AttentionCore) against the torch branch (the reference's four ops under autograd), alternated in one process.
 HIP events, median of 20 after 3 warm-up rounds; peak memory from torch.cuda.max_memory_allocated over one
-forward + backward. Usage: python tools/attn_bwd_bench.py [--out profiles/attention_backward_bench.txt]"""
+forward + backward. Usage: python tools/attn_bwd_bench.py [--out profiles/attention_backward_bench.txt]
+--hd 80 times the ViT-Huge/14 shape (B=64, N=257, H=16, head dim 80) instead of the two 64-wide shapes."""
 import argparse
 import os
 import statistics
@@ -14,7 +15,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from quantized_vit_amd import build  # noqa: E402
 from quantized_vit_amd.vit_model import ViTAttention  # noqa: E402
 
-SHAPES = [("ViT-B/16 b256", 256, 197, 12), ("ViT-L/16 @384 b128", 128, 577, 16)]
+SHAPES = {64: [("ViT-B/16 b256", 256, 197, 12), ("ViT-L/16 @384 b128", 128, 577, 16)],
+          80: [("ViT-H/14 b64", 64, 257, 16)]}
 REPS, WARM = 20, 3
 
 
@@ -41,17 +43,19 @@ def peak(attn, qkv, dO, B, N):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--hd", type=int, default=64, choices=(64, 80), help="head dim (selects the shapes)")
     a = ap.parse_args()
     build.build()
     dev = torch.device("cuda:0")
     lines = [f"device: {torch.cuda.get_device_name(0)}; median of {REPS}, HIP events, paths alternated"]
-    for name, B, N, H in SHAPES:
+    hd = a.hd
+    for name, B, N, H in SHAPES[hd]:
         torch.manual_seed(0)
-        hip = ViTAttention(H * 64, num_heads=H).to(dev).eval()
-        ref = ViTAttention(H * 64, num_heads=H).to(dev).eval()
+        hip = ViTAttention(H * hd, num_heads=H).to(dev).eval()
+        ref = ViTAttention(H * hd, num_heads=H).to(dev).eval()
         ref.hip_ok = lambda qkv: False          # the parent's route under autograd: torch ops
-        qkv = torch.randn(B, N, 3 * H * 64, device=dev)
-        dO = torch.randn(B, N, H * 64, device=dev)
+        qkv = torch.randn(B, N, 3 * H * hd, device=dev)
+        dO = torch.randn(B, N, H * hd, device=dev)
         t = {"hip": ([], []), "torch": ([], [])}
         for r in range(WARM + REPS):
             for key, m in (("hip", hip), ("torch", ref)):
@@ -60,7 +64,7 @@ def main():
                     t[key][0].append(f)
                     t[key][1].append(b)
         mem = {"hip": peak(hip, qkv, dO, B, N), "torch": peak(ref, qkv, dO, B, N)}
-        lines.append(f"{name}: B={B} N={N} H={H}   B*H*N*N*4 = {B * H * N * N * 4 / 2**20:.0f} MiB")
+        lines.append(f"{name}: B={B} N={N} H={H} hd={hd}   B*H*N*N*4 = {B * H * N * N * 4 / 2**20:.0f} MiB")
         for key in ("hip", "torch"):
             f, b = statistics.median(t[key][0]), statistics.median(t[key][1])
             lines.append(f"  {key:5s} forward {f:8.3f} ms  backward {b:8.3f} ms  total {f + b:8.3f} ms  "
