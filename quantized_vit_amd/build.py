@@ -25,8 +25,8 @@ SOURCES = ["quant_kernels.hip", "quant_backward.hip", "train_fuse.hip", "gemm_w4
 # sources with inline-asm register loads: their device assembly is kept beside the objects (the very code in the
 # library) for tools/asm_load_check.py (tests/test_asm_loads.py)
 ASM_CHECKED = ["gemm_w4a8.hip", "ultra_conv.hip"]
-HEADERS = ["qvit_common.h", "attn_common.h", "attn32.h", "ln_common.h", "quant_bwd_common.h", "ultra_quant_common.h",
-           "diag_stamps.h"]
+HEADERS = ["qvit_common.h", "attn_common.h", "attn32.h", "ln_common.h", "reduce_common.h", "quant_bwd_common.h",
+           "bf16x3.h", "ultra_quant_common.h", "diag_stamps.h"]
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}",

@@ -393,14 +393,12 @@ extern "C" int qvit_attention(const float* qkv, int64_t B, int64_t N, int64_t H,
   if (head_dim == HD80 && out_mode != QVIT_ATT_F32) return QVIT_EINVAL;  // the int8 epilogue is for head dim 64
   if (B < 0 || N <= 0 || H <= 0 || ldq < 3 * H * head_dim || ldo < H * head_dim) return QVIT_EINVAL;
   if (B * N > INT32_MAX || N > (1 << 20) || !(in_scale > 0.f)) return QVIT_EINVAL;
-  if ((ldq % 4) || (((uintptr_t)qkv) & 15)) return QVIT_EALIGN;
+  if ((ldq % 4) || qvit_misaligned(15, qkv)) return QVIT_EALIGN;
   if (out_mode == QVIT_ATT_F32) {
-    if ((ldo % 4) || (((uintptr_t)out) & 15)) return QVIT_EALIGN;
+    if ((ldo % 4) || qvit_misaligned(15, out)) return QVIT_EALIGN;
   } else if (out_mode == QVIT_ATT_I8) {
-    if ((ldo % 4) || (((uintptr_t)out) & 3)) return QVIT_EALIGN;
-    const int q = out_qtype & 0xff;
-    if (q != QVIT_QT_LINEAR && q != QVIT_QT_NONLINEAR && q != QVIT_QT_ULTRA_ACT) return QVIT_EINVAL;
-    if (q == QVIT_QT_ULTRA_ACT ? (out_levels < 1 || out_levels > 127) : (!out_d || !out_qm)) return QVIT_EINVAL;
+    if ((ldo % 4) || qvit_misaligned(3, out)) return QVIT_EALIGN;
+    if (qvit_out_quant_status(out_qtype, out_d, out_qm, out_levels)) return QVIT_EINVAL;
   } else {
     return QVIT_EINVAL;
   }
@@ -417,7 +415,7 @@ extern "C" int qvit_attention(const float* qkv, int64_t B, int64_t N, int64_t H,
   else
     hipLaunchKernelGGL(attn_kernel<1>, dim3((unsigned)nblk), dim3(256), 0, stream, qkv, (int)N, (int)H, ldq, scale,
                        in_scale, out, ldo, out_qtype, out_d, out_qm, out_t, out_levels);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 extern "C" int qvit_attention_split(const void* qkv_hi, const void* qkv_lo, int64_t B, int64_t N, int64_t H,
@@ -426,18 +424,16 @@ extern "C" int qvit_attention_split(const void* qkv_hi, const void* qkv_lo, int6
                                     const float* out_t, int out_levels, const void* epi_table,
                                     hipStream_t stream) {
   if (!qkv_hi || !qkv_lo || !out) return QVIT_ENULL;
-  if (epi_table && (((uintptr_t)epi_table) & 15)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, epi_table)) return QVIT_EALIGN;
   if (head_dim != HD) return QVIT_EINVAL;
   if (B < 0 || N <= 0 || H <= 0 || ldo < H * HD) return QVIT_EINVAL;
   if (B * N > INT32_MAX || N > (1 << 20) || !(in_scale > 0.f)) return QVIT_EINVAL;
-  if ((((uintptr_t)qkv_hi) & 15) || (((uintptr_t)qkv_lo) & 15)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, qkv_hi, qkv_lo)) return QVIT_EALIGN;
   if (out_mode == QVIT_ATT_F32) {
-    if ((ldo % 4) || (((uintptr_t)out) & 15)) return QVIT_EALIGN;
+    if ((ldo % 4) || qvit_misaligned(15, out)) return QVIT_EALIGN;
   } else if (out_mode == QVIT_ATT_I8) {
-    if ((ldo % 4) || (((uintptr_t)out) & 3)) return QVIT_EALIGN;
-    const int q = out_qtype & 0xff;
-    if (q != QVIT_QT_LINEAR && q != QVIT_QT_NONLINEAR && q != QVIT_QT_ULTRA_ACT) return QVIT_EINVAL;
-    if (q == QVIT_QT_ULTRA_ACT ? (out_levels < 1 || out_levels > 127) : (!out_d || !out_qm)) return QVIT_EINVAL;
+    if ((ldo % 4) || qvit_misaligned(3, out)) return QVIT_EALIGN;
+    if (qvit_out_quant_status(out_qtype, out_d, out_qm, out_levels)) return QVIT_EINVAL;
   } else {
     return QVIT_EINVAL;
   }
@@ -463,7 +459,7 @@ extern "C" int qvit_attention_split(const void* qkv_hi, const void* qkv_lo, int6
     hipLaunchKernelGGL(attn_split_kernel<1>, dim3((unsigned)grid), dim3(256), 0, stream, hi, lo, (int)N, (int)H,
                        (int)nblk, scale, in_scale, out, ldo, out_qtype, out_d, out_qm, out_t, out_levels,
                        reinterpret_cast<const int8_t*>(epi_table));
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 QVIT_ATT_STAMP_READER(qvit_att_stamps)  // diag_stamps.h: -DQVIT_ATT_STAMPS builds only

@@ -574,15 +574,13 @@ extern "C" int qvit_attention_backward(const float* qkv, const float* out, const
     return QVIT_EINVAL;
   if (B * N > INT32_MAX || N > (1 << 20) || !(in_scale > 0.f) || !(g_scale > 0.f)) return QVIT_EINVAL;
   if ((ldq % 4) || (ldo % 4) || (ldgo % 4) || (ldg % 4)) return QVIT_EALIGN;
-  if ((((uintptr_t)qkv) & 15) || (((uintptr_t)out) & 15) || (((uintptr_t)grad_out) & 15) ||
-      (((uintptr_t)grad_qkv) & 15))
-    return QVIT_EALIGN;
+  if (qvit_misaligned(15, qkv, out, grad_out, grad_qkv)) return QVIT_EALIGN;
   if (B == 0) return QVIT_OK;
   const int64_t need = qvit_attention_backward_workspace_bytes(B, N, H);
   if (need < 0) return QVIT_EINVAL;
   if (!workspace) return QVIT_ENULL;
   if (workspace_bytes < need) return QVIT_EINVAL;
-  if (((uintptr_t)workspace) & 15) return QVIT_EALIGN;
+  if (qvit_misaligned(15, workspace)) return QVIT_EALIGN;
   const int64_t BH = B * H;
   const int64_t nblk = BH * ((N + OG - 1) / OG);
   if (nblk > INT32_MAX) return QVIT_EINVAL;
@@ -597,7 +595,7 @@ extern "C" int qvit_attention_backward(const float* qkv, const float* out, const
                        (int)N, (int)H, ldq, ldgo, scale, in_scale, g_scale, grad_qkv, ldg, ws, (int)BH);
     hipLaunchKernelGGL((bwd_dkv_kernel<HD80, TWK80>), dim3((unsigned)nblk_k), dim3(256), 0, stream, qkv, grad_out,
                        (int)N, (int)H, ldq, ldgo, scale, in_scale, g_scale, grad_qkv, ldg, ws, (int)BH);
-    return qvit_hip_status(hipGetLastError());
+    return qvit_launch_status();
   }
   hipLaunchKernelGGL(bwd_prep_kernel<HD>, dim3((unsigned)BH), dim3(256), 0, stream, qkv, out, grad_out, (int)N,
                      (int)H, ldq, ldo, ldgo, in_scale, g_scale, ws);
@@ -605,5 +603,5 @@ extern "C" int qvit_attention_backward(const float* qkv, const float* out, const
                      (int)H, ldq, ldgo, scale, in_scale, g_scale, grad_qkv, ldg, ws, (int)BH);
   hipLaunchKernelGGL((bwd_dkv_kernel<HD, TW>), dim3((unsigned)nblk), dim3(256), 0, stream, qkv, grad_out, (int)N,
                      (int)H, ldq, ldgo, scale, in_scale, g_scale, grad_qkv, ldg, ws, (int)BH);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }

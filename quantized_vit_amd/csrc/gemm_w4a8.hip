@@ -1212,10 +1212,8 @@ extern "C" int qvit_epi_table_build(int epilogue, int out_qtype, const float* ou
   if (epilogue != QVIT_EPI_I8 && epilogue != QVIT_EPI_I8_GELU) return QVIT_EINVAL;
   if (nb < 1 || nb > QVIT_EPI_TABLE_MAX_NB || !(w > 0.f) || !std::isfinite(v_lo) || !std::isfinite(v_lo + w * nb))
     return QVIT_EINVAL;
-  const int q = out_qtype & 0xff;
-  if (q != QVIT_QT_LINEAR && q != QVIT_QT_NONLINEAR && q != QVIT_QT_ULTRA_ACT) return QVIT_EINVAL;
-  if (q == QVIT_QT_ULTRA_ACT ? (out_levels < 1 || out_levels > 127) : (!out_d || !out_qm)) return QVIT_EINVAL;
-  if (((uintptr_t)table) & 15) return QVIT_EALIGN;
+  if (qvit_out_quant_status(out_qtype, out_d, out_qm, out_levels)) return QVIT_EINVAL;
+  if (qvit_misaligned(15, table)) return QVIT_EALIGN;
   const int one = 1;
   hipError_t e = hipMemcpyAsync(reinterpret_cast<int8_t*>(table) + offsetof(EpiTableHdr, valid), &one, sizeof(int),
                                 hipMemcpyHostToDevice, stream);
@@ -1223,29 +1221,29 @@ extern "C" int qvit_epi_table_build(int epilogue, int out_qtype, const float* ou
   hipLaunchKernelGGL(epi_table_kernel, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, stream,
                      epilogue == QVIT_EPI_I8_GELU ? 1 : 0, out_qtype, out_d, out_qm, out_t, out_levels,
                      -(v_lo * (1.0f / w)), 1.0f / w, (int)nb, reinterpret_cast<int8_t*>(table));
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 extern "C" int qvit_pack_weight_w4r(const void* packed, int64_t npad, int64_t kpad, void* out, hipStream_t stream) {
   if (!packed || !out) return QVIT_ENULL;
   if (npad <= 0 || npad % BN || kpad <= 0 || kpad % KTILE || npad > INT32_MAX / 2 || kpad > 65536) return QVIT_EINVAL;
-  if ((((uintptr_t)packed) & 15) || (((uintptr_t)out) & 15)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, packed, out)) return QVIT_EALIGN;
   if (packed == out) return QVIT_EINVAL;  // not in place
   const int64_t units = npad * kpad / 16;  // 8-B slices (npad kpad / 2 bytes)
   hipLaunchKernelGGL(pack_w4r_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, stream,
                      reinterpret_cast<const int8_t*>(packed), reinterpret_cast<int8_t*>(out), units);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 extern "C" int qvit_pack_weight_w8r(const void* packed, int64_t npad, int64_t kpad, void* out, hipStream_t stream) {
   if (!packed || !out) return QVIT_ENULL;
   if (npad <= 0 || npad % BN || kpad <= 0 || kpad % KTILE || npad > INT32_MAX / 2 || kpad > 65536) return QVIT_EINVAL;
-  if ((((uintptr_t)packed) & 15) || (((uintptr_t)out) & 15)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, packed, out)) return QVIT_EALIGN;
   if (packed == out) return QVIT_EINVAL;  // not in place
   const int64_t units = npad * kpad / 16;  // 8-B source slices -> 16-B operands (npad kpad bytes out)
   hipLaunchKernelGGL(pack_w8r_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, stream,
                      reinterpret_cast<const int8_t*>(packed), reinterpret_cast<int8_t*>(out), units);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 extern "C" int qvit_gemm(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, int wfmt, int64_t N,
@@ -1257,22 +1255,20 @@ extern "C" int qvit_gemm(const int8_t* A, int64_t M, int64_t K, int64_t lda, con
   if (M < 0 || K <= 0 || K % KTILE || lda < K || N <= 0 || npad < N || npad % BN) return QVIT_EINVAL;
   if (M > INT32_MAX / 2 || npad > INT32_MAX / 2 || K > (1 << 24)) return QVIT_EINVAL;
   if (wfmt != QVIT_W8 && K > 65536) return QVIT_EINVAL;  // 16x-scaled int32 accumulation bound
-  if ((lda % 16) || (((uintptr_t)A) & 15) || (((uintptr_t)Wp) & 15)) return QVIT_EALIGN;
+  if ((lda % 16) || qvit_misaligned(15, A, Wp)) return QVIT_EALIGN;
   if (epilogue < QVIT_EPI_F32 || epilogue > QVIT_EPI_I32) return QVIT_EINVAL;
   const bool i8out = epilogue == QVIT_EPI_I8 || epilogue == QVIT_EPI_I8_GELU;
   if (ldc < N) return QVIT_EINVAL;
   if (i8out) {
-    if ((ldc % 4) || (((uintptr_t)C) & 3)) return QVIT_EALIGN;
-    const int q = out_qtype & 0xff;
-    if (q != QVIT_QT_LINEAR && q != QVIT_QT_NONLINEAR && q != QVIT_QT_ULTRA_ACT) return QVIT_EINVAL;
-    if (q == QVIT_QT_ULTRA_ACT ? (out_levels < 1 || out_levels > 127) : (!out_d || !out_qm)) return QVIT_EINVAL;
+    if ((ldc % 4) || qvit_misaligned(3, C)) return QVIT_EALIGN;
+    if (qvit_out_quant_status(out_qtype, out_d, out_qm, out_levels)) return QVIT_EINVAL;
   } else {
-    if ((ldc % 4) || (((uintptr_t)C) & 15)) return QVIT_EALIGN;
+    if ((ldc % 4) || qvit_misaligned(15, C)) return QVIT_EALIGN;
   }
   if (epilogue != QVIT_EPI_I32 && (!d_act || !d_wt)) return QVIT_ENULL;
-  if (bias && (((uintptr_t)bias) & 15)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, bias)) return QVIT_EALIGN;
   if (M == 0) return QVIT_OK;
-  if (epi_table && (((uintptr_t)epi_table) & 15)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, epi_table)) return QVIT_EALIGN;
   EpiArgs ep{d_act, d_wt, bias, out_qtype, out_d, out_qm, out_t, out_levels,
              (i8out ? reinterpret_cast<const int8_t*>(epi_table) : nullptr), 1, 1.f, 1.f, nullptr};
   if (wfmt == QVIT_W4) return dispatch_epi<QVIT_W4>(epilogue, A, M, K, lda, Wp, N, npad, C, ldc, ep, stream);
@@ -1293,14 +1289,10 @@ extern "C" int qvit_gemm_resid_ln(const int8_t* A, int64_t M, int64_t K, int64_t
     return QVIT_EINVAL;
   if (M > INT32_MAX / 2 || K > (1 << 24) || (wfmt == QVIT_W4 && K > 65536)) return QVIT_EINVAL;
   if (ldc < N || kpad_codes < N || ldcodes < kpad_codes || M * ldc * 4 > 0x7FFFFFFF) return QVIT_EINVAL;
-  if ((lda % 16) || (((uintptr_t)A) & 15) || (((uintptr_t)Wp) & 15)) return QVIT_EALIGN;
-  if ((ldc % 4) || (((uintptr_t)C) & 15) || (ldcodes % 4) || (((uintptr_t)codes) & 3)) return QVIT_EALIGN;
-  if ((((uintptr_t)counters) & 3) || (bias && (((uintptr_t)bias) & 15))) return QVIT_EALIGN;
-  if ((gamma && (((uintptr_t)gamma) & 15)) || (beta && (((uintptr_t)beta) & 15))) return QVIT_EALIGN;
-  if (ln_table && (((uintptr_t)ln_table) & 15)) return QVIT_EALIGN;
-  const int q = out_qtype & 0xff;
-  if (q != QVIT_QT_LINEAR && q != QVIT_QT_NONLINEAR && q != QVIT_QT_ULTRA_ACT) return QVIT_EINVAL;
-  if (q == QVIT_QT_ULTRA_ACT ? (out_levels < 1 || out_levels > 127) : (!out_d || !out_qm)) return QVIT_EINVAL;
+  if ((lda % 16) || qvit_misaligned(15, A, Wp)) return QVIT_EALIGN;
+  if ((ldc % 4) || (ldcodes % 4) || qvit_misaligned(15, C, bias, gamma, beta, ln_table)) return QVIT_EALIGN;
+  if (qvit_misaligned(3, codes, counters)) return QVIT_EALIGN;
+  if (qvit_out_quant_status(out_qtype, out_d, out_qm, out_levels)) return QVIT_EINVAL;
   if (M == 0) return QVIT_OK;
   // fresh arrival counters for this launch (the hand-off never depends on earlier launches)
   const hipError_t ez = hipMemsetAsync(counters, 0, (size_t)((M + 127) / 128) * sizeof(int32_t), stream);
@@ -1323,9 +1315,9 @@ extern "C" int qvit_gemm_qkv_split(const int8_t* A, int64_t M, int64_t K, int64_
   if (M > INT32_MAX / 2 || npad > INT32_MAX / 2 || K > (1 << 24)) return QVIT_EINVAL;
   if (seq <= 0 || seq > (1 << 20) || M % seq || !(in_scale > 0.f)) return QVIT_EINVAL;
   if (wfmt != QVIT_W8 && K > 65536) return QVIT_EINVAL;
-  if ((lda % 16) || (((uintptr_t)A) & 15) || (((uintptr_t)Wp) & 15)) return QVIT_EALIGN;
-  if ((((uintptr_t)qkv_hi) & 15) || (((uintptr_t)qkv_lo) & 15)) return QVIT_EALIGN;
-  if (bias && (((uintptr_t)bias) & 15)) return QVIT_EALIGN;
+  if ((lda % 16) || qvit_misaligned(15, A, Wp)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, qkv_hi, qkv_lo)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, bias)) return QVIT_EALIGN;
   if (M == 0) return QVIT_OK;
   EpiArgs ep{d_act, d_wt, bias, 0, nullptr, nullptr, nullptr, 0, nullptr, (int)seq, 1.0f / (float)seq, in_scale,
              reinterpret_cast<_Float16*>(qkv_lo)};

@@ -2,7 +2,7 @@
 // respect to the quantized weight,
 //   dW[n][k] = sum_m G[m][n] x_q[m][k] = d_act * sum_m G[m][n] A[m][k],   G fp32 (the output's gradient),
 // A the int8 activation codes the forward contracted (qvit_quantize_act_i8; x_q = d_act A).
-// Arithmetic (gemm_wonly.hip's): G = g1 + g2 + g3 with g1 = G truncated to bf16, g2 = (G - g1) truncated,
+// Arithmetic (bf16x3.h): G = g1 + g2 + g3 with g1 = G truncated to bf16, g2 = (G - g1) truncated,
 // g3 = G - g1 - g2 (each difference exact in fp32, g3 has at most 8 significant bits: a bf16 exactly); a code
 // has at most 7 significant bits, so every product g_i A is exact in fp32 and the three passes of
 // v_mfma_f32_16x16x32_bf16 sum G A with fp32 accumulation: an fp32 GEMM of G^T and A, the order of the m-term
@@ -22,20 +22,17 @@
 // images (a clamped row would be summed twice); columns n >= N / k >= K are not loaded (zero) and never stored.
 // Split over M: the output is small and M is huge, so the stages are dealt to `splits` workgroups per tile, each
 // writing its raw fp32 partial tile to the workspace [split][npad][kpad] (npad, kpad: N, K rounded up to 128);
-// wgrad_reduce_kernel sums the partials in ascending split order and multiplies by d_act. No atomics: the same
+// split_fold_kernel (reduce_common.h) sums the partials in ascending split order and multiplies by d_act. No atomics: the same
 // call gives the same bits. splits = min(16, stages, ceil(512 / tiles)): about two workgroups per CU.
 // Budget per workgroup: 64 KiB LDS, 256 threads, 154 VGPRs (64 of them accumulators), no scratch: two workgroups
 // per CU (2 waves per SIMD), set by the LDS (128 KiB of 160) and by __launch_bounds__.
-#include <algorithm>
-
-#include "qvit_common.h"
+#include "bf16x3.h"
+#include "reduce_common.h"
 
 namespace {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef short s8v __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
 
 constexpr int WG_BN = 128;            // G columns (dW rows) per tile
 constexpr int WG_BK = 128;            // code columns (dW columns) per tile
@@ -48,18 +45,6 @@ constexpr int WG_TARGET_WGS = 512;
 // byte offset of 16-B chunk ch (8 bf16) of row r in an image: serves the row-wise writes and the transposed reads
 QVIT_DEV int img_off(int r, int ch) { return 256 * r + 16 * (ch ^ (((r & 3) << 2) | ((r >> 2) & 3))); }
 
-QVIT_DEV float trunc_bf16(float x) { return __uint_as_float(__float_as_uint(x) & 0xFFFF0000u); }
-QVIT_DEV uint32_t hi16(float a, float b) {  // bf16 bits of a (low half) and b (high half); both exact bf16 values
-  return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xFFFF0000u);
-}
-// four signed bytes -> four bf16, exact
-QVIT_DEV void bytes_bf16(uint32_t d, uint32_t& lo, uint32_t& hi) {
-  const uint32_t u = d ^ 0x80808080u;  // unsigned byte = signed + 128
-  const float f0 = (float)(u & 0xff) - 128.f, f1 = (float)((u >> 8) & 0xff) - 128.f;
-  const float f2 = (float)((u >> 16) & 0xff) - 128.f, f3 = (float)(u >> 24) - 128.f;
-  lo = hi16(f0, f1);
-  hi = hi16(f2, f3);
-}
 QVIT_DEV s4v tr_read(const int8_t* p) {
   return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
       (__attribute__((address_space(3))) s4v*)(uintptr_t)(const __attribute__((address_space(3))) void*)p);
@@ -119,16 +104,8 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_kernel(const float* __restr
     for (int h = 0; h < 2; ++h) {
       uint32_t p1[4], p2[4], p3[4];
 #pragma unroll
-      for (int e = 0; e < 8; e += 2) {
-        const float a = gv[h][e >> 2][e & 3], c = gv[h][(e + 1) >> 2][(e + 1) & 3];
-        const float a1 = trunc_bf16(a), c1 = trunc_bf16(c);
-        const float ar = a - a1, cr_ = c - c1;  // exact
-        const float a2 = trunc_bf16(ar), c2 = trunc_bf16(cr_);
-        const float a3 = ar - a2, c3 = cr_ - c2;  // exact, <= 8 significant bits
-        p1[e >> 1] = hi16(a1, c1);
-        p2[e >> 1] = hi16(a2, c2);
-        p3[e >> 1] = hi16(a3, c3);
-      }
+      for (int e = 0; e < 8; e += 2)
+        split_bf16x3(gv[h][e >> 2][e & 3], gv[h][(e + 1) >> 2][(e + 1) & 3], p1[e >> 1], p2[e >> 1], p3[e >> 1]);
       int8_t* d = base + img_off(gr + 16 * h, gc);
       *reinterpret_cast<uint4*>(d) = make_uint4(p1[0], p1[1], p1[2], p1[3]);
       *reinterpret_cast<uint4*>(d + WG_IMG) = make_uint4(p2[0], p2[1], p2[2], p2[3]);
@@ -197,22 +174,6 @@ __global__ __launch_bounds__(256, 2) void gemm_wgrad_kernel(const float* __restr
     for (int kt = 0; kt < 4; ++kt) *reinterpret_cast<f4*>(pb + (int64_t)16 * nt * kpad + 16 * kt) = acc[kt][nt];
 }
 
-// dW[n][k] = d_act * sum_sp part[sp][n][k], the partials summed in ascending split order (splits == 0: zeros)
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ part, int splits, int N, int K,
-                                                            int npad, int kpad, const float* __restrict__ d_act,
-                                                            float* __restrict__ dW, int64_t ldw) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (int64_t)N * K) return;
-  const int n = (int)(i / K), k = (int)(i - (int64_t)n * K);
-  float v = 0.f;
-  if (splits > 0) {
-    float a = part[(int64_t)n * kpad + k];
-    for (int sp = 1; sp < splits; ++sp) a += part[((int64_t)sp * npad + n) * kpad + k];
-    v = (*d_act) * a;
-  }
-  dW[(int64_t)n * ldw + k] = v;
-}
-
 int64_t round128(int64_t v) { return (v + 127) / 128 * 128; }
 
 bool wgrad_sizes_ok(int64_t M, int64_t N, int64_t K) {
@@ -223,8 +184,7 @@ bool wgrad_sizes_ok(int64_t M, int64_t N, int64_t K) {
 int64_t wgrad_splits(int64_t M, int64_t N, int64_t K) {
   const int64_t tiles = (round128(N) / WG_BN) * (round128(K) / WG_BK);
   const int64_t nst = (M + WG_BM - 1) / WG_BM;
-  return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(WG_MAX_SPLITS, nst),
-                                                 (WG_TARGET_WGS + tiles - 1) / tiles));
+  return split_count(tiles, nst, WG_MAX_SPLITS, WG_TARGET_WGS);
 }
 
 }  // namespace
@@ -239,9 +199,7 @@ extern "C" int qvit_gemm_wgrad(const float* G, int64_t M, int64_t N, int64_t ldg
                                int64_t workspace_bytes, hipStream_t stream) {
   if (!G || !A || !d_act || !dW || !workspace) return QVIT_ENULL;
   if (!wgrad_sizes_ok(M, N, K) || ldg < N || lda < K || ldw < K) return QVIT_EINVAL;
-  if ((ldg % 4) || (lda % 16) || (((uintptr_t)G) & 15) || (((uintptr_t)A) & 15) || (((uintptr_t)workspace) & 15) ||
-      (((uintptr_t)dW) & 3))
-    return QVIT_EALIGN;
+  if ((ldg % 4) || (lda % 16) || qvit_misaligned(15, G, A, workspace) || qvit_misaligned(3, dW)) return QVIT_EALIGN;
   if (workspace_bytes < qvit_gemm_wgrad_workspace_bytes(M, N, K)) return QVIT_EINVAL;
   const int64_t npad = round128(N), kpad = round128(K);
   const int64_t splits = M == 0 ? 0 : wgrad_splits(M, N, K);
@@ -253,7 +211,7 @@ extern "C" int qvit_gemm_wgrad(const float* G, int64_t M, int64_t N, int64_t ldg
                        (int)splits, (int)npad, (int)kpad, part);
   }
   const unsigned rg = (unsigned)((N * K + 255) / 256);
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(rg), dim3(256), 0, stream, part, (int)splits, (int)N, (int)K,
-                     (int)npad, (int)kpad, d_act, dW, ldw);
-  return qvit_hip_status(hipGetLastError());
+  hipLaunchKernelGGL((split_fold_kernel<const float* __restrict__, int64_t>), dim3(rg), dim3(256), 0, stream, part,
+                     (int)splits, (int)N, (int)K, (int)npad, (int)kpad, d_act, dW, ldw);
+  return qvit_launch_status();
 }

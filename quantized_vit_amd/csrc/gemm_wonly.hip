@@ -33,12 +33,10 @@
 // and applies d_w / s and the bias.
 #include <algorithm>
 
-#include "qvit_common.h"
+#include "bf16x3.h"
 
 namespace {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int WO_BM = 64;        // x rows per tile
@@ -60,22 +58,10 @@ struct WoGeo {
 
 QVIT_DEV uint32_t nib16_lo(uint32_t p) { return (p << 4) & 0xF0F0F0F0u; }
 QVIT_DEV uint32_t nib16_hi(uint32_t p) { return p & 0xF0F0F0F0u; }
-QVIT_DEV uint32_t hi16(float a, float b) {  // bf16 bits of a (low half) and b (high half); both exact bf16 values
-  return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xFFFF0000u);
-}
-// four signed bytes -> four bf16 of mul * byte, exact (mul a power of two)
-QVIT_DEV void bytes_bf16(uint32_t d, uint32_t& lo, uint32_t& hi, float mul) {
-  const uint32_t u = d ^ 0x80808080u;  // unsigned byte = signed + 128
-  const float f0 = ((float)(u & 0xff) - 128.f) * mul, f1 = ((float)((u >> 8) & 0xff) - 128.f) * mul;
-  const float f2 = ((float)((u >> 16) & 0xff) - 128.f) * mul, f3 = ((float)(u >> 24) - 128.f) * mul;
-  lo = hi16(f0, f1);
-  hi = hi16(f2, f3);
-}
 // convolution geometry (CONV kernels); L = OH OW output pixels per image, kreal = C kh kw
 struct WoConv {
   int C, H, W, kh, kw, sh, sw, ph, pw, dh, dw, OW, L, kreal;
 };
-QVIT_DEV float trunc_bf16(float x) { return __uint_as_float(__float_as_uint(x) & 0xFFFF0000u); }
 
 template <int WFMT, bool CONV>
 __global__ __launch_bounds__(256, WoGeo<WFMT>::MINB) void gemm_wonly_kernel(
@@ -156,16 +142,8 @@ __global__ __launch_bounds__(256, WoGeo<WFMT>::MINB) void gemm_wonly_kernel(
     int8_t* base = smem + b * G::STAGE;
     uint32_t p1[8], p2[8], p3[8];
 #pragma unroll
-    for (int e = 0; e < 16; e += 2) {
-      const float a = xv[e >> 2][e & 3], c = xv[(e + 1) >> 2][(e + 1) & 3];
-      const float a1 = trunc_bf16(a), c1 = trunc_bf16(c);
-      const float ar = a - a1, cr = c - c1;  // exact
-      const float a2 = trunc_bf16(ar), c2 = trunc_bf16(cr);
-      const float a3 = ar - a2, c3 = cr - c2;  // exact, <= 8 significant bits
-      p1[e >> 1] = hi16(a1, c1);
-      p2[e >> 1] = hi16(a2, c2);
-      p3[e >> 1] = hi16(a3, c3);
-    }
+    for (int e = 0; e < 16; e += 2)
+      split_bf16x3(xv[e >> 2][e & 3], xv[(e + 1) >> 2][(e + 1) & 3], p1[e >> 1], p2[e >> 1], p3[e >> 1]);
     int8_t* d = base + xr * WO_PITCH + 32 * xq;
     *reinterpret_cast<uint4*>(d) = make_uint4(p1[0], p1[1], p1[2], p1[3]);
     *reinterpret_cast<uint4*>(d + 16) = make_uint4(p1[4], p1[5], p1[6], p1[7]);
@@ -215,8 +193,8 @@ __global__ __launch_bounds__(256, WoGeo<WFMT>::MINB) void gemm_wonly_kernel(
 #pragma unroll
         for (int e = 0; e < 4; ++e)
           bytes_bf16((uint32_t)wf[e], h[2 * e], h[2 * e + 1], G::PARTS - 1 - q == 2 ? 65536.f : G::PARTS - 1 - q == 1 ? 256.f : 1.f);
-        wb[q][r][0] = __builtin_bit_cast(bf8, make_uint4(h[0], h[1], h[2], h[3]));
-        wb[q][r][1] = __builtin_bit_cast(bf8, make_uint4(h[4], h[5], h[6], h[7]));
+        wb[q][r][0] = as_bf8(h[0], h[1], h[2], h[3]);
+        wb[q][r][1] = as_bf8(h[4], h[5], h[6], h[7]);
       }
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
@@ -446,16 +424,7 @@ __global__ __launch_bounds__(NW_WAVES * 64) void conv_wonly_narrow_kernel(
     {
       uint32_t p1[8], p2[8], p3[8];
 #pragma unroll
-      for (int e = 0; e < 16; e += 2) {
-        const float a = xv[e], c = xv[e + 1];
-        const float a1 = trunc_bf16(a), c1 = trunc_bf16(c);
-        const float ar = a - a1, cr = c - c1;
-        const float a2 = trunc_bf16(ar), c2 = trunc_bf16(cr);
-        const float a3 = ar - a2, c3 = cr - c2;
-        p1[e >> 1] = hi16(a1, c1);
-        p2[e >> 1] = hi16(a2, c2);
-        p3[e >> 1] = hi16(a3, c3);
-      }
+      for (int e = 0; e < 16; e += 2) split_bf16x3(xv[e], xv[e + 1], p1[e >> 1], p2[e >> 1], p3[e >> 1]);
       if constexpr (PAIR) {  // lanes 32 .. 63 hold the second tile: split into {lo, 0} and {hi, 0}
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
@@ -469,19 +438,19 @@ __global__ __launch_bounds__(NW_WAVES * 64) void conv_wonly_narrow_kernel(
             a2[d] = w2[0]; b2[d] = w2[1];
             a3[d] = w3[0]; b3[d] = w3[1];
           }
-          xs[0][c] = __builtin_bit_cast(bf8, make_uint4(a1[0], a1[1], a1[2], a1[3]));
-          xs[1][c] = __builtin_bit_cast(bf8, make_uint4(a2[0], a2[1], a2[2], a2[3]));
-          xs[2][c] = __builtin_bit_cast(bf8, make_uint4(a3[0], a3[1], a3[2], a3[3]));
-          xt[0][c] = __builtin_bit_cast(bf8, make_uint4(b1[0], b1[1], b1[2], b1[3]));
-          xt[1][c] = __builtin_bit_cast(bf8, make_uint4(b2[0], b2[1], b2[2], b2[3]));
-          xt[2][c] = __builtin_bit_cast(bf8, make_uint4(b3[0], b3[1], b3[2], b3[3]));
+          xs[0][c] = as_bf8(a1[0], a1[1], a1[2], a1[3]);
+          xs[1][c] = as_bf8(a2[0], a2[1], a2[2], a2[3]);
+          xs[2][c] = as_bf8(a3[0], a3[1], a3[2], a3[3]);
+          xt[0][c] = as_bf8(b1[0], b1[1], b1[2], b1[3]);
+          xt[1][c] = as_bf8(b2[0], b2[1], b2[2], b2[3]);
+          xt[2][c] = as_bf8(b3[0], b3[1], b3[2], b3[3]);
         }
       } else {
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-          xs[0][c] = __builtin_bit_cast(bf8, make_uint4(p1[4 * c], p1[4 * c + 1], p1[4 * c + 2], p1[4 * c + 3]));
-          xs[1][c] = __builtin_bit_cast(bf8, make_uint4(p2[4 * c], p2[4 * c + 1], p2[4 * c + 2], p2[4 * c + 3]));
-          xs[2][c] = __builtin_bit_cast(bf8, make_uint4(p3[4 * c], p3[4 * c + 1], p3[4 * c + 2], p3[4 * c + 3]));
+          xs[0][c] = as_bf8(p1[4 * c], p1[4 * c + 1], p1[4 * c + 2], p1[4 * c + 3]);
+          xs[1][c] = as_bf8(p2[4 * c], p2[4 * c + 1], p2[4 * c + 2], p2[4 * c + 3]);
+          xs[2][c] = as_bf8(p3[4 * c], p3[4 * c + 1], p3[4 * c + 2], p3[4 * c + 3]);
         }
       }
     }
@@ -499,9 +468,9 @@ __global__ __launch_bounds__(NW_WAVES * 64) void conv_wonly_narrow_kernel(
       }
       uint32_t h[8];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) bytes_bf16((uint32_t)wf[e], h[2 * e], h[2 * e + 1], 1.f);
-      wb[t][0] = __builtin_bit_cast(bf8, make_uint4(h[0], h[1], h[2], h[3]));
-      wb[t][1] = __builtin_bit_cast(bf8, make_uint4(h[4], h[5], h[6], h[7]));
+      for (int e = 0; e < 4; ++e) bytes_bf16((uint32_t)wf[e], h[2 * e], h[2 * e + 1]);
+      wb[t][0] = as_bf8(h[0], h[1], h[2], h[3]);
+      wb[t][1] = as_bf8(h[4], h[5], h[6], h[7]);
     }
 #pragma unroll
     for (int c = 0; c < 2; ++c)
@@ -604,7 +573,7 @@ int narrow_launch(const NarrowGeo& g, const float* X, int64_t M, const int8_t* w
 #undef QVIT_NW_T
 #undef QVIT_NW
 #undef QVIT_NW2
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 // shared launch of the GEMM (CONV = false) and the implicit-GEMM convolution (CONV = true); arguments checked
@@ -624,7 +593,7 @@ int wonly_launch(const float* X, int64_t M, int64_t K, int64_t ldx, const void* 
   // holds the partials)
   const int64_t nk = K / WO_BK;
   int64_t splits = 1;
-  if (ntiles < 128 && nk >= 2 && workspace && !(((uintptr_t)workspace) & 15)) {
+  if (ntiles < 128 && nk >= 2 && workspace && !qvit_misaligned(15, workspace)) {
     splits = std::min<int64_t>(nk, (256 + ntiles - 1) / ntiles);
     while (splits > 1 && splits * M * npad * 4 > workspace_bytes) --splits;
   }
@@ -649,7 +618,7 @@ int wonly_launch(const float* X, int64_t M, int64_t K, int64_t ldx, const void* 
       hipLaunchKernelGGL(wonly_reduce_kernel<QVIT_W8>, dim3(rg), dim3(256), 0, stream, workspace, (int)splits, (int)M,
                          (int)N, (int)npad, d_wt, bias, Y, ldy, L);
   }
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 }  // namespace
@@ -662,8 +631,7 @@ extern "C" int qvit_gemm_wonly(const float* X, int64_t M, int64_t K, int64_t ldx
   if (M < 0 || K <= 0 || K % QVIT_TILE_K || ldx < K || N <= 0 || npad < N || npad % WO_BN || ldy < N)
     return QVIT_EINVAL;
   if (M > INT32_MAX / 2 || npad > INT32_MAX / 2 || K > (1 << 24)) return QVIT_EINVAL;
-  if ((ldx % 4) || (((uintptr_t)X) & 15) || (((uintptr_t)Wp) & 15)) return QVIT_EALIGN;
-  if ((ldy % 4) || (((uintptr_t)Y) & 15) || (bias && (((uintptr_t)bias) & 15))) return QVIT_EALIGN;
+  if ((ldx % 4) || (ldy % 4) || qvit_misaligned(15, X, Wp, Y, bias)) return QVIT_EALIGN;
   if (M == 0) return QVIT_OK;
   return wonly_launch<false>(X, M, K, ldx, Wp, wfmt, N, npad, d_wt, bias, Y, ldy, workspace, workspace_bytes,
                              WoConv{}, stream);
@@ -690,7 +658,7 @@ int conv_args(const float* X, int64_t B, int64_t C, int64_t H, int64_t W, int kh
     return QVIT_EINVAL;
   M = B * OH * OW;
   if (M > INT32_MAX / 2 || OH * OW > INT32_MAX / 2) return QVIT_EINVAL;
-  if ((((uintptr_t)Wp) & 15) || (bias && (((uintptr_t)bias) & 15))) return QVIT_EALIGN;
+  if (qvit_misaligned(15, Wp, bias)) return QVIT_EALIGN;
   cg = WoConv{(int)C, (int)H, (int)W, kh, kw, sh, sw, ph, pw, dh, dw, (int)OW, (int)(OH * OW), (int)kreal};
   return QVIT_OK;
 }

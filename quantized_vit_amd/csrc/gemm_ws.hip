@@ -356,7 +356,7 @@ int ws_launch(int epi, const int8_t* A, int64_t M, const void* Wp, int64_t N, vo
   else
     hipLaunchKernelGGL((gemm_ws_kernel<NTN, NKC, QVIT_EPI_I8>), dim3(256), dim3(WS_NT), 0, stream, A, (int)M, w, c,
                        ldc, panels, ep);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 }  // namespace
@@ -384,11 +384,8 @@ extern "C" int qvit_gemm_a32(const int8_t* A, int64_t M, int64_t K, const void* 
   if (!qvit_gemm_a32_fits(K, wfmt, N, npad, epilogue)) return QVIT_EINVAL;
   if (M < 0 || M > INT32_MAX / 2 || ldc < N) return QVIT_EINVAL;
   if ((M + 63) / 64 * 64 * K > (int64_t)0xFFFFFFFF) return QVIT_EINVAL;  // 32-bit activation offsets
-  const int q = out_qtype & 0xff;
-  if (q != QVIT_QT_LINEAR && q != QVIT_QT_NONLINEAR && q != QVIT_QT_ULTRA_ACT) return QVIT_EINVAL;
-  if (q == QVIT_QT_ULTRA_ACT ? (out_levels < 1 || out_levels > 127) : (!out_d || !out_qm)) return QVIT_EINVAL;
-  if ((((uintptr_t)A) & 15) || (((uintptr_t)Wp) & 15) || (ldc % 16) || (((uintptr_t)C) & 15)) return QVIT_EALIGN;
-  if ((bias && (((uintptr_t)bias) & 15)) || (epi_table && (((uintptr_t)epi_table) & 15))) return QVIT_EALIGN;
+  if (qvit_out_quant_status(out_qtype, out_d, out_qm, out_levels)) return QVIT_EINVAL;
+  if ((ldc % 16) || qvit_misaligned(15, A, Wp, C, bias, epi_table)) return QVIT_EALIGN;
   if (M == 0) return QVIT_OK;
   const WsArgs ep{d_act, d_wt, bias, out_qtype, out_d, out_qm, out_t, out_levels,
                   reinterpret_cast<const int8_t*>(epi_table)};

@@ -482,15 +482,12 @@ static int qkv_attention_launch(const int8_t* A, int64_t B, int64_t N, int64_t K
   if (B * N > INT32_MAX / 2 || !(in_scale > 0.f)) return QVIT_EINVAL;
   // the kernel addresses A and Wp with 32-bit byte offsets from the base pointers
   if (B * N * lda > (int64_t)0xFFFFFFFF - 64 || npad * K / 2 > (int64_t)0xFFFFFFFF) return QVIT_EINVAL;
-  if ((lda % 16) || (((uintptr_t)A) & 15) || (((uintptr_t)Wp) & 15)) return QVIT_EALIGN;
-  if (epi_table && (((uintptr_t)epi_table) & 15)) return QVIT_EALIGN;
+  if ((lda % 16) || qvit_misaligned(15, A, Wp, epi_table)) return QVIT_EALIGN;
   if (out_mode == QVIT_ATT_F32) {
-    if ((ldo % 4) || (((uintptr_t)out) & 15)) return QVIT_EALIGN;
+    if ((ldo % 4) || qvit_misaligned(15, out)) return QVIT_EALIGN;
   } else if (out_mode == QVIT_ATT_I8) {
-    if ((ldo % 4) || (((uintptr_t)out) & 3)) return QVIT_EALIGN;
-    const int q = out_qtype & 0xff;
-    if (q != QVIT_QT_LINEAR && q != QVIT_QT_NONLINEAR && q != QVIT_QT_ULTRA_ACT) return QVIT_EINVAL;
-    if (q == QVIT_QT_ULTRA_ACT ? (out_levels < 1 || out_levels > 127) : (!out_d || !out_qm)) return QVIT_EINVAL;
+    if ((ldo % 4) || qvit_misaligned(3, out)) return QVIT_EALIGN;
+    if (qvit_out_quant_status(out_qtype, out_d, out_qm, out_levels)) return QVIT_EINVAL;
   } else {
     return QVIT_EINVAL;
   }
@@ -523,7 +520,7 @@ static int qkv_attention_launch(const int8_t* A, int64_t B, int64_t N, int64_t K
   else QVIT_QA_LAUNCH_K(1, tab);
 #undef QVIT_QA_LAUNCH_K
 #undef QVIT_QA_LAUNCH
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 extern "C" int qvit_qkv_attention(const int8_t* A, int64_t B, int64_t N, int64_t K, int64_t lda, const void* Wp,

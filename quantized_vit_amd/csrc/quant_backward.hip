@@ -16,16 +16,6 @@
 
 namespace {
 
-constexpr int kGridCap = 1024;   // 4 blocks per CU; a grid-stride loop covers the rest
-constexpr int kVec = 4;          // floats per 16-byte access
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-inline int backward_grid(int64_t n) {
-  const int64_t g = cdiv(n / kVec, kThreads);
-  return (int)(g < 1 ? 1 : (g < kGridCap ? g : kGridCap));
-}
-
 template <bool NONLINEAR, bool DGE>
 QVIT_DEV float4 backward_vec(const float4& x, const float4& g, const BwdParams& b, double& sd, double& sq,
                              double& st) {
@@ -71,29 +61,7 @@ __global__ __launch_bounds__(kThreads) void quant_backward_kernel(
   if (e < n) grad_x[e] = backward_element<NONLINEAR, DGE>(x[e], grad_out[e], b, sd, sq, st);
 
   block_sum3(sd, sq, st, lds);
-  if (threadIdx.x == 0) {
-    double* out = partials + (int64_t)blockIdx.x * 3;
-    out[0] = sd; out[1] = sq; out[2] = st;
-  }
-}
-
-// Second stage, one block: thread i adds the partials of blocks i, i + 256, ... in that order, then the block
-// reduces as above. nblocks == 0 writes three zeros.
-__global__ __launch_bounds__(kThreads) void quant_backward_finish_kernel(const double* partials, int nblocks,
-                                                                         float* grad_scalars) {
-  __shared__ double lds[kWaves][3];
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  for (int j = threadIdx.x; j < nblocks; j += kThreads) {
-    s0 += partials[(int64_t)j * 3 + 0];
-    s1 += partials[(int64_t)j * 3 + 1];
-    s2 += partials[(int64_t)j * 3 + 2];
-  }
-  block_sum3(s0, s1, s2, lds);
-  if (threadIdx.x == 0) {
-    grad_scalars[0] = (float)s0;
-    grad_scalars[1] = (float)s1;
-    grad_scalars[2] = (float)s2;
-  }
+  if (threadIdx.x == 0) store_partial3(partials, sd, sq, st);   // folded by scalar_finish_kernel
 }
 
 }  // namespace
@@ -102,7 +70,7 @@ extern "C" {
 
 int64_t qvit_quant_backward_workspace_bytes(int64_t n) {
   if (n < 0) return QVIT_EINVAL;
-  return (int64_t)backward_grid(n) * 3 * (int64_t)sizeof(double);
+  return (int64_t)stream_grid(n, kVec) * 3 * (int64_t)sizeof(double);
 }
 
 int qvit_quant_backward(const float* x, const float* grad_out, int64_t n, int qtype, const float* d_quant,
@@ -110,20 +78,17 @@ int qvit_quant_backward(const float* x, const float* grad_out, int64_t n, int qt
                         float* grad_x, float* grad_scalars, void* workspace, int64_t workspace_bytes,
                         hipStream_t stream) {
   if (!x || !grad_out || !grad_x || !grad_scalars || !d_quant || !q_m || !workspace) return QVIT_ENULL;
-  const int qt = qtype & 0xff;
-  if ((qtype & ~(0xff | QVIT_QT_FORCE_CAREFUL)) != 0 || (qt != QVIT_QT_LINEAR && qt != QVIT_QT_NONLINEAR))
-    return QVIT_EINVAL;
-  const bool nonlinear = qt == QVIT_QT_NONLINEAR;
+  bool nonlinear = false;
+  if (qvit_backward_qtype_status(qtype, nonlinear)) return QVIT_EINVAL;
   if (nonlinear && !t_quant) return QVIT_ENULL;
   if (n < 0 || !(dge_k >= 0.f) || (dge_k > 0.f && nonlinear)) return QVIT_EINVAL;
   if (workspace_bytes < qvit_quant_backward_workspace_bytes(n)) return QVIT_EINVAL;
-  if ((((uintptr_t)x) | ((uintptr_t)grad_out) | ((uintptr_t)grad_x)) & 15) return QVIT_EALIGN;
-  if ((uintptr_t)workspace & 7) return QVIT_EALIGN;
+  if (qvit_misaligned(15, x, grad_out, grad_x) || qvit_misaligned(7, workspace)) return QVIT_EALIGN;
 
   double* partials = static_cast<double*>(workspace);
   int grid = 0;
   if (n > 0) {
-    grid = backward_grid(n);
+    grid = stream_grid(n, kVec);
     const dim3 g(grid), blk(kThreads);
     if (nonlinear)
       hipLaunchKernelGGL((quant_backward_kernel<true, false>), g, blk, 0, stream, x, grad_out, n, qtype, d_quant,
@@ -137,9 +102,9 @@ int qvit_quant_backward(const float* x, const float* grad_out, int64_t n, int qt
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return qvit_hip_status(e);
   }
-  hipLaunchKernelGGL(quant_backward_finish_kernel, dim3(1), dim3(kThreads), 0, stream, partials, grid,
+  hipLaunchKernelGGL(scalar_finish_kernel, dim3(1), dim3(kThreads), 0, stream, partials, grid,
                      grad_scalars);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 }  // extern "C"

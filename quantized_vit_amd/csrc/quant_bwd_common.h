@@ -1,40 +1,11 @@
 // Device code of the quantizer backward shared by quant_backward.hip (qvit_quant_backward) and train_fuse.hip
-// (the same backward behind a recomputed LayerNorm or GELU): the per-call uniforms, one element's terms, and the
-// fixed-order sums of a 256-thread block. See quant_backward.hip for the table of regions and the mask rules.
+// (the same backward behind a recomputed LayerNorm or GELU): the per-call uniforms and one element's terms; the
+// fixed-order sums they leave through are reduce_common.h's. See quant_backward.hip for the table of regions and the
+// mask rules.
 #pragma once
-#include "qvit_common.h"
+#include "reduce_common.h"
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-
-// wave64 sum in a fixed order; lane 0 holds the result
-QVIT_DEV double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-  return v;
-}
-
-// Sums of one block: every wave reduces its lanes, wave w leaves its three sums in lds[w], thread 0 adds the
-// waves in index order. Returns the totals in thread 0 (other threads: unspecified).
-QVIT_DEV void block_sum3(double& s0, double& s1, double& s2, double (*lds)[3]) {
-  s0 = wave_sum(s0);
-  s1 = wave_sum(s1);
-  s2 = wave_sum(s2);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    lds[wave][0] = s0; lds[wave][1] = s1; lds[wave][2] = s2;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    s0 = lds[0][0]; s1 = lds[0][1]; s2 = lds[0][2];
-#pragma unroll
-    for (int w = 1; w < kWaves; ++w) {
-      s0 += lds[w][0]; s1 += lds[w][1]; s2 += lds[w][2];
-    }
-  }
-}
 
 // The wave-uniform values of one call.
 struct BwdParams {
@@ -112,6 +83,26 @@ QVIT_DEV float backward_element(float x, float g, const BwdParams& b, double& sd
     gx = (gx < -3.f) ? -3.f : ((gx > 3.f) ? 3.f : gx);                    // :265, NaN passes through
   }
   return gx;
+}
+
+// The three scalar gradients (d_quant, q_m, t_quant) of a quantizer backward from its nblocks x 3 partials, one
+// block: thread i adds the partials of blocks i, i + 256, ... in that order, then the block reduces as block_sum3.
+// nblocks == 0 writes three zeros.
+__global__ __launch_bounds__(kThreads) void scalar_finish_kernel(const double* partials, int nblocks,
+                                                                 float* grad_scalars) {
+  __shared__ double lds[kWaves][3];
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  for (int j = threadIdx.x; j < nblocks; j += kThreads) {
+    s0 += partials[(int64_t)j * 3 + 0];
+    s1 += partials[(int64_t)j * 3 + 1];
+    s2 += partials[(int64_t)j * 3 + 2];
+  }
+  block_sum3(s0, s1, s2, lds);
+  if (threadIdx.x == 0) {
+    grad_scalars[0] = (float)s0;
+    grad_scalars[1] = (float)s1;
+    grad_scalars[2] = (float)s2;
+  }
 }
 
 }  // namespace

@@ -5,23 +5,14 @@
 // allows), so the bound is HBM bandwidth: 5 bytes moved per element.
 #include "qvit_common.h"
 #include "ln_common.h"
-
-#include <algorithm>
+#include "reduce_common.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-inline int grid_for(int64_t work, int threads) {
-  int64_t g = cdiv(work, threads);
-  const int64_t cap = 256 * 16;  // 16 blocks per CU, grid-stride beyond
-  return (int)(g < cap ? (g > 0 ? g : 1) : cap);
-}
-
 // ---- activation quantizer: one thread = 16 columns of one row -> one 16-byte store ----------
-__global__ __launch_bounds__(kThreads) void quantize_act_kernel(
+// GELU: codes = quantize(GELU(x)) (qvit_gelu_quant_i8), else codes = quantize(x) (qvit_quantize_act_i8)
+template <bool GELU>
+__global__ __launch_bounds__(kThreads) void rows_to_codes_kernel(
     const float* __restrict__ x, int64_t rows, int64_t cols, int64_t ldx, int qtype,
     const float* d, const float* qm, const float* t, int levels, int8_t* __restrict__ codes,
     int64_t ldc, int64_t kpad) {
@@ -51,7 +42,9 @@ __global__ __launch_bounds__(kThreads) void quantize_act_kernel(
       uint32_t acc = 0;
 #pragma unroll
       for (int b = 0; b < 4; ++b) {
-        const int8_t k = to_i8_sat(quant_code(v[4 * i + b], p));
+        float a = v[4 * i + b];
+        if constexpr (GELU) a = (c0 + 4 * i + b < cols) ? gelu_ref(a) : 0.f;
+        const int8_t k = to_i8_sat(quant_code(a, p));
         acc |= ((uint32_t)(uint8_t)k) << (8 * b);
       }
       w[i] = acc;
@@ -431,41 +424,44 @@ const char* qvit_strerror(int code) {
 
 const char* qvit_version(void) { return "qvit_hip 0.1 gfx950"; }
 
-static bool qtype_ok(int qtype) {
-  const int q = qtype & 0xff;
-  return (qtype & ~(0xff | QVIT_QT_FORCE_CAREFUL)) == 0 &&
-         (q == QVIT_QT_LINEAR || q == QVIT_QT_NONLINEAR || q == QVIT_QT_ULTRA_ACT);
-}
-
-static bool qptrs_ok(int qtype, const float* d, const float* qm, int levels) {
-  if ((qtype & 0xff) == QVIT_QT_ULTRA_ACT) return levels >= 1 && levels <= 127;
-  return d != nullptr && qm != nullptr;
-}
-
 int qvit_quantize_act_i8(const float* x, int64_t rows, int64_t cols, int64_t ldx, int qtype,
                          const float* d_quant, const float* q_m, const float* t_quant, int levels,
                          int8_t* codes, int64_t ldc, int64_t kpad, hipStream_t stream) {
   if (!x || !codes) return QVIT_ENULL;
-  if (!qtype_ok(qtype) || !qptrs_ok(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
+  if (qvit_quant_status(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
   if (rows < 0 || cols < 0 || ldx < cols || kpad < cols || kpad % 16 || ldc < kpad) return QVIT_EINVAL;
-  if ((ldc % 16) || (((uintptr_t)codes) & 15)) return QVIT_EALIGN;
+  if ((ldc % 16) || qvit_misaligned(15, codes)) return QVIT_EALIGN;
   if (rows == 0 || kpad == 0) return QVIT_OK;
   const int64_t work = rows * (kpad / 16);
-  hipLaunchKernelGGL(quantize_act_kernel, dim3(grid_for(work, kThreads)), dim3(kThreads), 0, stream,
+  hipLaunchKernelGGL(rows_to_codes_kernel<false>, dim3(grid_for(work, kThreads)), dim3(kThreads), 0, stream,
                      x, rows, cols, ldx, qtype, d_quant, q_m, t_quant, levels, codes, ldc, kpad);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
+}
+
+int qvit_gelu_quant_i8(const float* h, int64_t rows, int64_t cols, int64_t ldh, int qtype, const float* d_quant,
+                       const float* q_m, const float* t_quant, int levels, int8_t* codes, int64_t ldc, int64_t kpad,
+                       hipStream_t stream) {
+  if (!h || !codes) return QVIT_ENULL;
+  if (qvit_quant_status(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
+  if (rows < 0 || cols < 0 || ldh < cols || kpad < cols || kpad % 16 || ldc < kpad) return QVIT_EINVAL;
+  if ((ldc % 16) || qvit_misaligned(15, codes)) return QVIT_EALIGN;
+  if (rows == 0 || kpad == 0) return QVIT_OK;
+  const int64_t work = rows * (kpad / 16);
+  hipLaunchKernelGGL(rows_to_codes_kernel<true>, dim3(grid_for(work, kThreads)), dim3(kThreads), 0, stream, h, rows,
+                     cols, ldh, qtype, d_quant, q_m, t_quant, levels, codes, ldc, kpad);
+  return qvit_launch_status();
 }
 
 int qvit_fake_quant_f32(const float* x, int64_t n, int qtype, const float* d_quant,
                         const float* q_m, const float* t_quant, int levels, float* y,
                         hipStream_t stream) {
   if (!x || !y) return QVIT_ENULL;
-  if (!qtype_ok(qtype) || !qptrs_ok(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
+  if (qvit_quant_status(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
   if (n < 0) return QVIT_EINVAL;
   if (n == 0) return QVIT_OK;
   hipLaunchKernelGGL(fake_quant_kernel, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, stream, x,
                      n, qtype, d_quant, q_m, t_quant, levels, y);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int qvit_gelu_f32(const float* x, int64_t n, float* y, hipStream_t stream) {
@@ -473,7 +469,7 @@ int qvit_gelu_f32(const float* x, int64_t n, float* y, hipStream_t stream) {
   if (n < 0) return QVIT_EINVAL;
   if (n == 0) return QVIT_OK;
   hipLaunchKernelGGL(gelu_kernel, dim3(grid_for(n, kThreads)), dim3(kThreads), 0, stream, x, n, y);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int qvit_pack_weight(const float* w, int64_t n, int64_t k, int64_t ldw, int qtype,
@@ -481,12 +477,12 @@ int qvit_pack_weight(const float* w, int64_t n, int64_t k, int64_t ldw, int qtyp
                      void* packed, int64_t npad, int64_t kpad, int32_t* overflow,
                      hipStream_t stream) {
   if (!w || !packed) return QVIT_ENULL;
-  const int q = qtype & 0xff;
-  if (!qtype_ok(qtype) || q == QVIT_QT_ULTRA_ACT || !d_quant || !q_m) return QVIT_EINVAL;
+  // (a weight quantizer: ULTRA_ACT is none)
+  if ((qtype & 0xff) == QVIT_QT_ULTRA_ACT || qvit_quant_status(qtype, d_quant, q_m, 0)) return QVIT_EINVAL;
   if (wfmt != QVIT_W4 && wfmt != QVIT_W8) return QVIT_EINVAL;
   if (n <= 0 || k <= 0 || ldw < k || npad < n || kpad < k) return QVIT_EINVAL;
   if (npad % QVIT_TILE_N || kpad % QVIT_TILE_K) return QVIT_EINVAL;
-  if (((uintptr_t)packed) & 15) return QVIT_EALIGN;
+  if (qvit_misaligned(15, packed)) return QVIT_EALIGN;
   const int64_t work = npad * (kpad / 8);
   if (wfmt == QVIT_W4) {
     hipLaunchKernelGGL(pack_weight_kernel<QVIT_W4>, dim3(grid_for(work, kThreads)), dim3(kThreads),
@@ -497,7 +493,7 @@ int qvit_pack_weight(const float* w, int64_t n, int64_t k, int64_t ldw, int qtyp
                        0, stream, w, n, k, ldw, qtype, d_quant, q_m, t_quant, packed, npad, kpad,
                        overflow);
   }
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int qvit_pad_bias(const float* bias, int64_t n, float* out, int64_t npad, hipStream_t stream) {
@@ -506,7 +502,7 @@ int qvit_pad_bias(const float* bias, int64_t n, float* out, int64_t npad, hipStr
   if (npad == 0) return QVIT_OK;
   hipLaunchKernelGGL(pad_bias_kernel, dim3(grid_for(npad, kThreads)), dim3(kThreads), 0, stream,
                      bias, n, out, npad);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int qvit_im2col_quant_i8(const float* x, int64_t B, int64_t C, int64_t H, int64_t W, int kh,
@@ -514,7 +510,7 @@ int qvit_im2col_quant_i8(const float* x, int64_t B, int64_t C, int64_t H, int64_
                          const float* d_quant, const float* q_m, const float* t_quant, int levels,
                          int8_t* codes, int64_t ldc, int64_t kpad, hipStream_t stream) {
   if (!x || !codes) return QVIT_ENULL;
-  if (!qtype_ok(qtype) || !qptrs_ok(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
+  if (qvit_quant_status(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
   if (B < 0 || C <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || ph < 0 ||
       pw < 0 || dh <= 0 || dw <= 0)
     return QVIT_EINVAL;
@@ -522,7 +518,7 @@ int qvit_im2col_quant_i8(const float* x, int64_t B, int64_t C, int64_t H, int64_
   const int64_t OW = (W + 2 * pw - (int64_t)dw * (kw - 1) - 1) / sw + 1;
   const int64_t K = C * kh * kw;
   if (OH <= 0 || OW <= 0 || kpad < K || kpad % 16 || ldc < kpad) return QVIT_EINVAL;
-  if ((ldc % 16) || (((uintptr_t)codes) & 15)) return QVIT_EALIGN;
+  if ((ldc % 16) || qvit_misaligned(15, codes)) return QVIT_EALIGN;
   if (B == 0) return QVIT_OK;
   const int64_t work = B * OH * OW * (kpad / 16);
   const int64_t lim = (int64_t)INT32_MAX - 2 * (int64_t)256 * 16 * kThreads;  // headroom for the grid stride
@@ -534,7 +530,7 @@ int qvit_im2col_quant_i8(const float* x, int64_t B, int64_t C, int64_t H, int64_
     hipLaunchKernelGGL(im2col_quant_kernel<int64_t>, dim3(grid_for(work, kThreads)), dim3(kThreads), 0, stream,
                        x, B, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw, OH, OW, qtype, d_quant, q_m,
                        t_quant, levels, codes, ldc, kpad);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int qvit_layernorm_quant_i8(const float* x, int64_t rows, int64_t cols, int64_t ldx,
@@ -543,13 +539,12 @@ int qvit_layernorm_quant_i8(const float* x, int64_t rows, int64_t cols, int64_t 
                             int levels, int8_t* codes, int64_t ldc, int64_t kpad,
                             const void* code_table, hipStream_t stream) {
   if (!x || !codes) return QVIT_ENULL;
-  if (code_table && (((uintptr_t)code_table) & 15)) return QVIT_EALIGN;
-  if (!qtype_ok(qtype) || !qptrs_ok(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
+  if (qvit_misaligned(15, code_table)) return QVIT_EALIGN;
+  if (qvit_quant_status(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
   if (rows < 0 || cols <= 0 || ldx < cols || kpad < cols || ldc < kpad) return QVIT_EINVAL;
-  if (((ldc & 3) != 0) || (((uintptr_t)codes) & 3)) return QVIT_EALIGN;
+  if (((ldc & 3) != 0) || qvit_misaligned(3, codes)) return QVIT_EALIGN;
   if (rows == 0) return QVIT_OK;
-  const bool reg = ((cols & 3) == 0) && ((ldx & 3) == 0) && ((((uintptr_t)x) & 15) == 0) &&
-                   (!gamma || (((uintptr_t)gamma) & 15) == 0) && (!beta || (((uintptr_t)beta) & 15) == 0);
+  const bool reg = ((cols & 3) == 0) && ((ldx & 3) == 0) && !qvit_misaligned(15, x, gamma, beta);
   const int nv = (int)((cols + 255) / 256);
   const dim3 grid((unsigned)((rows + 3) / 4));
   if (reg && nv <= 4) {  // persistent: as many workgroups as are co-resident, the table read once per workgroup
@@ -580,7 +575,7 @@ int qvit_layernorm_quant_i8(const float* x, int64_t rows, int64_t cols, int64_t 
     else if (nv <= 3) QVIT_LN_P(3);
     else QVIT_LN_P(4);
 #undef QVIT_LN_P
-    return qvit_hip_status(hipGetLastError());
+    return qvit_launch_status();
   }
 #define QVIT_LN_REG(NV)                                                                                   \
   hipLaunchKernelGGL(layernorm_quant_reg_kernel<NV>, grid, dim3(kThreads), 0, stream, x, rows, cols, ldx, \
@@ -590,7 +585,7 @@ int qvit_layernorm_quant_i8(const float* x, int64_t rows, int64_t cols, int64_t 
     hipLaunchKernelGGL(layernorm_quant_kernel, dim3(grid_for(rows * 64, kThreads)), dim3(kThreads), 0, stream, x,
                        rows, cols, ldx, gamma, beta, eps, qtype, d_quant, q_m, t_quant, levels, codes, ldc, kpad);
 #undef QVIT_LN_REG
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int qvit_layernorm_quant_i8_t32(const float* x, int64_t rows, int64_t cols, int64_t ldx, const float* gamma,
@@ -598,12 +593,10 @@ int qvit_layernorm_quant_i8_t32(const float* x, int64_t rows, int64_t cols, int6
                                 const float* t_quant, int levels, int8_t* codes, int64_t kpad, const void* code_table,
                                 hipStream_t stream) {
   if (!x || !codes) return QVIT_ENULL;
-  if (code_table && (((uintptr_t)code_table) & 15)) return QVIT_EALIGN;
-  if (!qtype_ok(qtype) || !qptrs_ok(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
+  if (qvit_misaligned(15, code_table)) return QVIT_EALIGN;
+  if (qvit_quant_status(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
   if (rows < 0 || cols <= 0 || cols > 1024 || (cols & 3) || ldx < cols || kpad < cols || (kpad & 63)) return QVIT_EINVAL;
-  if ((ldx & 3) || (((uintptr_t)x) & 15) || (gamma && (((uintptr_t)gamma) & 15)) || (beta && (((uintptr_t)beta) & 15)) ||
-      (((uintptr_t)codes) & 15))
-    return QVIT_EALIGN;
+  if ((ldx & 3) || qvit_misaligned(15, x, gamma, beta, codes)) return QVIT_EALIGN;
   if (rows == 0) return QVIT_OK;
   static const int cus = [] {
     int dev = 0, n = 0;
@@ -632,7 +625,7 @@ int qvit_layernorm_quant_i8_t32(const float* x, int64_t rows, int64_t cols, int6
   else if (nv <= 3) QVIT_LN_T(3);
   else QVIT_LN_T(4);
 #undef QVIT_LN_T
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 }  // extern "C"

@@ -270,6 +270,41 @@ QVIT_DEV void dma16s(const void* sbase, uint32_t voff, uint32_t lds_base) {
       : "memory");
 }
 
+// ---- host-side argument checks of the entry points ----------------------------------------------------------
+// Inside an entry point the ORDER of the checks is part of the C ABI: a call that breaks two rules gets the status
+// of the first (tests/test_capi_rejections.py pins it per entry point). These helpers name the rules; where an entry
+// point's rule really differs it stays open-coded there, with a comment.
 static inline int qvit_hip_status(hipError_t e) {
   return e == hipSuccess ? QVIT_OK : (QVIT_EHIP - (int)e);
+}
+// the tail of an entry point: the status of the launches it made
+static inline int qvit_launch_status() { return qvit_hip_status(hipGetLastError()); }
+
+// true when a pointer has a bit of `mask` set (15: 16-byte alignment); a null pointer passes
+template <typename... P>
+static inline bool qvit_misaligned(uintptr_t mask, const P*... p) {
+  return ((... | (uintptr_t)p) & mask) != 0;
+}
+
+// a qtype carries the enum in its low byte and at most the QVIT_QT_FORCE_CAREFUL flag above it
+static inline bool qvit_qtype_flags_ok(int qtype) { return (qtype & ~(0xff | QVIT_QT_FORCE_CAREFUL)) == 0; }
+
+// The output quantizer of an int8 epilogue (GEMM, attention): a known enum and the scalars it reads, ULTRA_ACT a
+// level count in 1..127, the others d and q_m. The flag bits are not looked at here.
+static inline int qvit_out_quant_status(int qtype, const float* d, const float* qm, int levels) {
+  const int q = qtype & 0xff;
+  if (q != QVIT_QT_LINEAR && q != QVIT_QT_NONLINEAR && q != QVIT_QT_ULTRA_ACT) return QVIT_EINVAL;
+  if (q == QVIT_QT_ULTRA_ACT ? (levels < 1 || levels > 127) : (!d || !qm)) return QVIT_EINVAL;
+  return QVIT_OK;
+}
+// The quantizer of the quantizer kernels (quant_kernels.hip): the same behind the flag check.
+static inline int qvit_quant_status(int qtype, const float* d, const float* qm, int levels) {
+  return qvit_qtype_flags_ok(qtype) ? qvit_out_quant_status(qtype, d, qm, levels) : QVIT_EINVAL;
+}
+// The quantizer of a backward pass: the flag check, then LINEAR or NONLINEAR only.
+static inline int qvit_backward_qtype_status(int qtype, bool& nonlinear) {
+  const int q = qtype & 0xff;
+  if (!qvit_qtype_flags_ok(qtype) || (q != QVIT_QT_LINEAR && q != QVIT_QT_NONLINEAR)) return QVIT_EINVAL;
+  nonlinear = q == QVIT_QT_NONLINEAR;
+  return QVIT_OK;
 }

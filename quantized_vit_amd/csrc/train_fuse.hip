@@ -6,7 +6,8 @@
 //                                  (ln_row_values), the quantizer backward at (y, grad_y) (backward_element of
 //                                  qvit_quant_backward), then the LayerNorm backward. Reads x and grad_y once,
 //                                  writes grad_x once: 3 rows cols 4 bytes, plus the partials below.
-//   qvit_gelu_quant_i8             codes = quantize(GELU(h)): qvit_quantize_act_i8 with gelu_ref in front.
+//   (qvit_gelu_quant_i8, the forward of the GELU pair, is qvit_quantize_act_i8's kernel with gelu_ref in front: it
+//   lives beside it in quant_kernels.hip.)
 //   qvit_gelu_quant_backward       qvit_quant_backward at a = GELU(h), grad_h = GELU'(h) * gy: 3 n 4 bytes.
 //
 // Reductions leave the kernels through per-workgroup partials folded in a fixed order by a second launch (no float
@@ -17,11 +18,7 @@
 
 namespace {
 
-constexpr int kGridCap = 1024;   // 4 blocks per CU; grid-stride loops cover the rest
-constexpr int kVec = 4;          // floats per 16-byte access
 constexpr int kLnMaxCols = 2048; // 8 float4 per lane
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- LayerNorm + quantizer backward: one wave per row -------------------------------------------------------
 inline int ln_bwd_grid(int64_t rows) {
@@ -116,10 +113,7 @@ __global__ __launch_bounds__(kThreads) void layernorm_quant_backward_kernel(
   }
 
   block_sum3(sd, sq, st, lds);
-  if (tid == 0) {
-    double* out = partials + (int64_t)blockIdx.x * 3;
-    out[0] = sd; out[1] = sq; out[2] = st;
-  }
+  if (tid == 0) store_partial3(partials, sd, sq, st);
   if (col_partials == nullptr) return;
   // column sums of the block: the waves add into LDS one after the other, in wave order
   __syncthreads();   // gamma / beta are no longer read
@@ -149,7 +143,7 @@ __global__ __launch_bounds__(kThreads) void layernorm_quant_backward_kernel(
   }
 }
 
-// Second stage. The last block folds the scalar partials as quant_backward_finish_kernel does. Every other block
+// Second stage. The last block folds the scalar partials as scalar_finish_kernel does. Every other block
 // owns kFinCols columns: the workgroup partials are cut into kFinChunks equal runs, thread (chunk, column) adds its
 // run of its column in ascending workgroup order, and the chunk-0 thread adds the kFinChunks run sums in ascending
 // order (one thread walking all 1024 partials of a column alone is a chain of dependent-latency loads that costs
@@ -162,6 +156,7 @@ __global__ __launch_bounds__(kThreads) void layernorm_quant_backward_finish_kern
   __shared__ double lds[kWaves][3];
   __shared__ double run[kFinChunks][kFinCols][2];
   if (blockIdx.x == gridDim.x - 1) {
+    // (scalar_finish_kernel's loop, kept here: behind a helper the compiler allocates the sums differently)
     double s0 = 0.0, s1 = 0.0, s2 = 0.0;
     for (int j = threadIdx.x; j < nblocks; j += kThreads) {
       s0 += partials[(int64_t)j * 3 + 0];
@@ -204,58 +199,7 @@ __global__ __launch_bounds__(kThreads) void layernorm_quant_backward_finish_kern
   }
 }
 
-// ---- GELU + quantizer -------------------------------------------------------------------------------------------
-inline int grid_for(int64_t work, int threads) {
-  const int64_t g = cdiv(work, threads);
-  const int64_t cap = 256 * 16;  // as quantize_act_kernel
-  return (int)(g < cap ? (g > 0 ? g : 1) : cap);
-}
-
-// quantize_act_kernel (quant_kernels.hip) with GELU in front: one thread = 16 columns of one row -> one 16-byte store
-__global__ __launch_bounds__(kThreads) void gelu_quant_kernel(
-    const float* __restrict__ h, int64_t rows, int64_t cols, int64_t ldh, int qtype, const float* d, const float* qm,
-    const float* t, int levels, int8_t* __restrict__ codes, int64_t ldc, int64_t kpad) {
-  const QParams p = load_qparams(qtype, d, qm, t, levels);
-  const int64_t chunks_per_row = kpad / 16;
-  const int64_t total = rows * chunks_per_row;
-  const bool vec = ((ldh & 3) == 0) && ((((uintptr_t)h) & 15) == 0);
-  for (int64_t id = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; id < total;
-       id += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t r = id / chunks_per_row;
-    const int64_t c0 = (id - r * chunks_per_row) * 16;
-    const float* src = h + r * ldh + c0;
-    float v[16];
-    if (vec && c0 + 16 <= cols) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float4 f = *reinterpret_cast<const float4*>(src + 4 * i);
-        v[4 * i + 0] = f.x; v[4 * i + 1] = f.y; v[4 * i + 2] = f.z; v[4 * i + 3] = f.w;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = (c0 + i < cols) ? src[i] : 0.f;
-    }
-    uint32_t w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      uint32_t acc = 0;
-#pragma unroll
-      for (int bb = 0; bb < 4; ++bb) {
-        const float a = (c0 + 4 * i + bb < cols) ? gelu_ref(v[4 * i + bb]) : 0.f;
-        const int8_t k = to_i8_sat(quant_code(a, p));
-        acc |= ((uint32_t)(uint8_t)k) << (8 * bb);
-      }
-      w[i] = acc;
-    }
-    *reinterpret_cast<uint4*>(codes + r * ldc + c0) = make_uint4(w[0], w[1], w[2], w[3]);
-  }
-}
-
-inline int gelu_bwd_grid(int64_t n) {
-  const int64_t g = cdiv(n / kVec, kThreads);
-  return (int)(g < 1 ? 1 : (g < kGridCap ? g : kGridCap));
-}
-
+// ---- GELU + quantizer backward (the forward, qvit_gelu_quant_i8: quant_kernels.hip's rows_to_codes_kernel) -------
 // GELU'(v) = Phi(v) + v phi(v) from the pieces gelu_ref computes: Phi = (1 + erf(v / sqrt 2)) / 2 with the same erf,
 // phi(v) = exp(-v^2 / 2) / sqrt(2 pi) with the same exponential (the compiler shares them with gelu_ref's).
 QVIT_DEV float gelu_grad(float x) {
@@ -307,34 +251,7 @@ __global__ __launch_bounds__(kThreads) void gelu_quant_backward_kernel(
   if (e < n) grad_h[e] = gelu_backward_element<NONLINEAR>(h[e], grad_y[e], b, sd, sq, st);
 
   block_sum3(sd, sq, st, lds);
-  if (threadIdx.x == 0) {
-    double* out = partials + (int64_t)blockIdx.x * 3;
-    out[0] = sd; out[1] = sq; out[2] = st;
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void scalar_finish_kernel(const double* partials, int nblocks,
-                                                                 float* grad_scalars) {
-  __shared__ double lds[kWaves][3];
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-  for (int j = threadIdx.x; j < nblocks; j += kThreads) {
-    s0 += partials[(int64_t)j * 3 + 0];
-    s1 += partials[(int64_t)j * 3 + 1];
-    s2 += partials[(int64_t)j * 3 + 2];
-  }
-  block_sum3(s0, s1, s2, lds);
-  if (threadIdx.x == 0) {
-    grad_scalars[0] = (float)s0;
-    grad_scalars[1] = (float)s1;
-    grad_scalars[2] = (float)s2;
-  }
-}
-
-bool backward_qtype(int qtype, bool& nonlinear) {
-  const int qt = qtype & 0xff;
-  if ((qtype & ~(0xff | QVIT_QT_FORCE_CAREFUL)) != 0 || (qt != QVIT_QT_LINEAR && qt != QVIT_QT_NONLINEAR)) return false;
-  nonlinear = qt == QVIT_QT_NONLINEAR;
-  return true;
+  if (threadIdx.x == 0) store_partial3(partials, sd, sq, st);
 }
 
 }  // namespace
@@ -356,15 +273,13 @@ int qvit_layernorm_quant_backward(const float* x, int64_t rows, int64_t cols, in
   if (!x || !gamma || !beta || !grad_y || !grad_x || !grad_scalars || !d_quant || !q_m || !workspace)
     return QVIT_ENULL;
   bool nonlinear = false;
-  if (!backward_qtype(qtype, nonlinear)) return QVIT_EINVAL;
+  if (qvit_backward_qtype_status(qtype, nonlinear)) return QVIT_EINVAL;
   if (nonlinear && !t_quant) return QVIT_ENULL;
   if (rows < 0 || cols <= 0 || ldx < cols || ldg < cols || ldo < cols) return QVIT_EINVAL;
   if (workspace_bytes < qvit_layernorm_quant_backward_workspace_bytes(rows, cols)) return QVIT_EINVAL;
   if ((cols & 3) || cols > kLnMaxCols || (ldx & 3) || (ldg & 3) || (ldo & 3)) return QVIT_EALIGN;
-  if ((((uintptr_t)x) | ((uintptr_t)gamma) | ((uintptr_t)beta) | ((uintptr_t)grad_y) | ((uintptr_t)grad_x) |
-       ((uintptr_t)workspace)) & 15)
-    return QVIT_EALIGN;
-  if ((grad_gamma && (((uintptr_t)grad_gamma) & 3)) || (grad_beta && (((uintptr_t)grad_beta) & 3))) return QVIT_EALIGN;
+  if (qvit_misaligned(15, x, gamma, beta, grad_y, grad_x, workspace)) return QVIT_EALIGN;
+  if (qvit_misaligned(3, grad_gamma, grad_beta)) return QVIT_EALIGN;
 
   int grid = 0;
   double* partials = static_cast<double*>(workspace);
@@ -398,30 +313,12 @@ int qvit_layernorm_quant_backward(const float* x, int64_t rows, int64_t cols, in
   const int col_blocks = (grad_gamma || grad_beta) ? (int)cdiv(cols, kFinCols) : 0;
   hipLaunchKernelGGL(layernorm_quant_backward_finish_kernel, dim3(col_blocks + 1), dim3(kThreads), 0, stream, partials,
                      colp, grid, (int)cols, grad_gamma, grad_beta, grad_scalars);
-  return qvit_hip_status(hipGetLastError());
-}
-
-int qvit_gelu_quant_i8(const float* h, int64_t rows, int64_t cols, int64_t ldh, int qtype, const float* d_quant,
-                       const float* q_m, const float* t_quant, int levels, int8_t* codes, int64_t ldc, int64_t kpad,
-                       hipStream_t stream) {
-  if (!h || !codes) return QVIT_ENULL;
-  const int q = qtype & 0xff;
-  if ((qtype & ~(0xff | QVIT_QT_FORCE_CAREFUL)) != 0 ||
-      (q != QVIT_QT_LINEAR && q != QVIT_QT_NONLINEAR && q != QVIT_QT_ULTRA_ACT))
-    return QVIT_EINVAL;
-  if (q == QVIT_QT_ULTRA_ACT ? (levels < 1 || levels > 127) : (!d_quant || !q_m)) return QVIT_EINVAL;
-  if (rows < 0 || cols < 0 || ldh < cols || kpad < cols || kpad % 16 || ldc < kpad) return QVIT_EINVAL;
-  if ((ldc % 16) || (((uintptr_t)codes) & 15)) return QVIT_EALIGN;
-  if (rows == 0 || kpad == 0) return QVIT_OK;
-  const int64_t work = rows * (kpad / 16);
-  hipLaunchKernelGGL(gelu_quant_kernel, dim3(grid_for(work, kThreads)), dim3(kThreads), 0, stream, h, rows, cols, ldh,
-                     qtype, d_quant, q_m, t_quant, levels, codes, ldc, kpad);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int64_t qvit_gelu_quant_backward_workspace_bytes(int64_t n) {
   if (n < 0) return QVIT_EINVAL;
-  return (int64_t)gelu_bwd_grid(n) * 3 * (int64_t)sizeof(double);
+  return (int64_t)stream_grid(n, kVec) * 3 * (int64_t)sizeof(double);
 }
 
 int qvit_gelu_quant_backward(const float* h, const float* grad_y, int64_t n, int qtype, const float* d_quant,
@@ -429,17 +326,16 @@ int qvit_gelu_quant_backward(const float* h, const float* grad_y, int64_t n, int
                              float* grad_scalars, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
   if (!h || !grad_y || !grad_h || !grad_scalars || !d_quant || !q_m || !workspace) return QVIT_ENULL;
   bool nonlinear = false;
-  if (!backward_qtype(qtype, nonlinear)) return QVIT_EINVAL;
+  if (qvit_backward_qtype_status(qtype, nonlinear)) return QVIT_EINVAL;
   if (nonlinear && !t_quant) return QVIT_ENULL;
   if (n < 0) return QVIT_EINVAL;
   if (workspace_bytes < qvit_gelu_quant_backward_workspace_bytes(n)) return QVIT_EINVAL;
-  if ((((uintptr_t)h) | ((uintptr_t)grad_y) | ((uintptr_t)grad_h)) & 15) return QVIT_EALIGN;
-  if ((uintptr_t)workspace & 7) return QVIT_EALIGN;
+  if (qvit_misaligned(15, h, grad_y, grad_h) || qvit_misaligned(7, workspace)) return QVIT_EALIGN;
 
   double* partials = static_cast<double*>(workspace);
   int grid = 0;
   if (n > 0) {
-    grid = gelu_bwd_grid(n);
+    grid = stream_grid(n, kVec);
     if (nonlinear)
       hipLaunchKernelGGL(gelu_quant_backward_kernel<true>, dim3(grid), dim3(kThreads), 0, stream, h, grad_y, n, qtype,
                          d_quant, q_m, t_quant, clip_lo, clip_hi, grad_h, partials);
@@ -450,7 +346,7 @@ int qvit_gelu_quant_backward(const float* h, const float* grad_y, int64_t n, int
     if (e != hipSuccess) return qvit_hip_status(e);
   }
   hipLaunchKernelGGL(scalar_finish_kernel, dim3(1), dim3(kThreads), 0, stream, partials, grid, grad_scalars);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 }  // extern "C"

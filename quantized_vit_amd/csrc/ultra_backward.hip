@@ -6,7 +6,7 @@
 //     g_u = g;  g_t = g / m - sgn(t) [|t| == m] S / (m^2 c),  S = sum_i g_i t_i,  c = #{i : |t_i| == m}
 //     (torch's full-reduction max hands its gradient to the tied elements in equal shares);  g_w = g_t (1 - t^2).
 //   t and m are ultra_quant_common.h's, the forward's routines: the tie set is the one the forward saw. S and c
-//   leave the streaming pass through quant_backward.hip's scheme: per-thread double accumulation, the fixed-order
+//   leave the streaming pass through reduce_common.h's scheme: per-thread double accumulation, the fixed-order
 //   wave / block tree, one partial pair per block in the caller's workspace, a one-block fold in index order. No
 //   float atomics: two calls give the same bits. Masks select, they never multiply: a NaN in g_i is in g_w[i] and,
 //   through S, in every tied element; a NaN w_i is in g_w[i] (and in S).
@@ -15,7 +15,7 @@
 // qvit_conv_wgrad  dWq[n][c][ky][kx] = (1 / levels) sum_{b,oy,ox} G[b][n][oy][ox] k_x[b][c][iy][ix],
 //   iy = oy sh - ph + ky dh, ix = ox sw - pw + kx dw, k_x = rint(X levels) the codes of X = k / levels (the
 //   output of activation_quantize_fn, max-pooled or not), out-of-image taps zero.
-//   Arithmetic (gemm_wgrad.hip's): G = g1 + g2 + g3 exactly, three truncated bf16 terms; a code (<= 127) is a bf16
+//   Arithmetic (bf16x3.h): G = g1 + g2 + g3 exactly, three truncated bf16 terms; a code (<= 127) is a bf16
 //   exactly; every product is exact in fp32 and v_mfma_f32_16x16x32_bf16 accumulates in fp32; one multiply by
 //   1 / levels ends it. A NaN / inf in G[b][n][.][.] makes row n of dWq NaN (NaN times a zero code is NaN) and no
 //   other row.
@@ -28,25 +28,14 @@
 //   read the same G and the same X window) straight into MFMA registers. No LDS, no barrier, no inline assembly.
 //   Rows m >= M, columns n >= N and k >= K are not loaded (zero operands); a lane ends with dWq[n = fr][4 fq + j].
 //   Split / fold: the M range (in stages of 32) is dealt to `splits` waves per tile, each writing its raw fp32
-//   partial tile to the workspace [split][npad][kpad] (N, K rounded up to 64); conv_wgrad_fold_kernel sums them in
-//   ascending split order and multiplies by 1 / levels. No atomics: the same call gives the same bits.
+//   partial tile to the workspace [split][npad][kpad] (N, K rounded up to 64); split_fold_kernel (reduce_common.h)
+//   sums them in ascending split order and multiplies by 1 / levels. No atomics: the same call gives the same bits.
 //   splits = max(1, min(256, ceil(M / 32), ceil(2048 / tiles))): two waves per SIMD on 256 CUs.
-#include <algorithm>
-
-#include "quant_bwd_common.h"
+#include "bf16x3.h"
+#include "reduce_common.h"
 #include "ultra_quant_common.h"
 
 namespace {
-
-constexpr int kGridCap = 1024;   // 4 blocks per CU; a grid-stride loop covers the rest
-constexpr int kVec = 4;          // floats per 16-byte access
-
-inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
-inline int stream_grid(int64_t n, int per_thread) {
-  const int64_t g = cdiv(n / per_thread, kThreads);
-  return (int)(g < 1 ? 1 : (g < kGridCap ? g : kGridCap));
-}
 
 // ---- weight quantizer backward --------------------------------------------------------------------------------
 // workspace: [0] the bits of m (unsigned), [8] the tie term's coefficient S / (m^2 c) (float), from byte 16 one
@@ -75,10 +64,7 @@ __global__ __launch_bounds__(kThreads) void ultra_wq_sums_kernel(const float* __
     if (fabsf(t) == m) c += 1.0;
   }
   block_sum3(s, c, unused, lds);
-  if (threadIdx.x == 0) {
-    partials[2 * (int64_t)blockIdx.x] = s;
-    partials[2 * (int64_t)blockIdx.x + 1] = c;
-  }
+  if (threadIdx.x == 0) store_partial2(partials, blockIdx.x, s, c);
 }
 
 // one block: thread i adds the partials of blocks i, i + 256, ... in that order, then the block tree
@@ -86,6 +72,7 @@ __global__ __launch_bounds__(kThreads) void ultra_wq_finish_kernel(const double*
                                                                    const unsigned* __restrict__ maxbits,
                                                                    float* __restrict__ coef) {
   __shared__ double lds[kWaves][3];
+  // (fold_partials2's loop, kept here: through the helper the compiler swaps the registers of the two sums)
   double s = 0.0, c = 0.0, unused = 0.0;
   for (int j = threadIdx.x; j < nblocks; j += kThreads) {
     s += partials[2 * (int64_t)j];
@@ -132,9 +119,6 @@ __global__ __launch_bounds__(kThreads) void ultra_act_backward_kernel(const floa
 }
 
 // ---- conv weight gradient -------------------------------------------------------------------------------------
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 constexpr int CW_TN = 64;            // dWq rows (output channels) per wave tile
 constexpr int CW_TK = 64;            // dWq columns (c, ky, kx) per wave tile
 constexpr int CW_BM = 32;            // m per stage: one MFMA contraction
@@ -145,14 +129,6 @@ constexpr int CW_FAR = -(1 << 29);   // row base of a stage row m >= M: every ta
 struct ConvGeo {
   int B, C, H, W, N, kh, kw, sh, sw, ph, pw, dh, dw, OH, OW, K, M;
 };
-
-QVIT_DEV float trunc_bf16(float x) { return __uint_as_float(__float_as_uint(x) & 0xFFFF0000u); }
-QVIT_DEV uint32_t hi16(float a, float b) {  // bf16 bits of a (low half) and b (high half); both exact bf16 values
-  return (__float_as_uint(a) >> 16) | (__float_as_uint(b) & 0xFFFF0000u);
-}
-QVIT_DEV bf8 as_bf8(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  return __builtin_bit_cast(bf8, make_uint4(a, b, c, d));
-}
 
 // part[sp][n][k] (n < npad, k < kpad) = sum over the split's m of G[m][n] code[m][k]
 __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict__ G, const float* __restrict__ X,
@@ -263,16 +239,7 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict
         }
         uint32_t p1[4], p2[4], p3[4];
 #pragma unroll
-        for (int e = 0; e < 8; e += 2) {
-          const float a = gv[e], c = gv[e + 1];
-          const float a1 = trunc_bf16(a), c1 = trunc_bf16(c);
-          const float ar = a - a1, cr = c - c1;   // exact
-          const float a2 = trunc_bf16(ar), c2 = trunc_bf16(cr);
-          const float a3 = ar - a2, c3 = cr - c2;   // exact, <= 8 significant bits
-          p1[e >> 1] = hi16(a1, c1);
-          p2[e >> 1] = hi16(a2, c2);
-          p3[e >> 1] = hi16(a3, c3);
-        }
+        for (int e = 0; e < 8; e += 2) split_bf16x3(gv[e], gv[e + 1], p1[e >> 1], p2[e >> 1], p3[e >> 1]);
         const bf8 g1 = as_bf8(p1[0], p1[1], p1[2], p1[3]);
         const bf8 g2 = as_bf8(p2[0], p2[1], p2[2], p2[3]);
         const bf8 g3 = as_bf8(p3[0], p3[1], p3[2], p3[3]);
@@ -294,22 +261,6 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const float* __restrict
   for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
     for (int kt = 0; kt < 4; ++kt) *reinterpret_cast<f4*>(pb + (int64_t)16 * nt * kpad + 16 * kt) = acc[kt][nt];
-}
-
-// dW[n][k] = inv_levels * sum_sp part[sp][n][k], the partials summed in ascending split order (splits == 0: zeros)
-__global__ __launch_bounds__(256) void conv_wgrad_fold_kernel(const float* __restrict__ part, int splits, int N,
-                                                              int K, int npad, int kpad, float inv_levels,
-                                                              float* __restrict__ dW) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (int64_t)N * K) return;
-  const int n = (int)(i / K), k = (int)(i - (int64_t)n * K);
-  float v = 0.f;
-  if (splits > 0) {
-    float a = part[(int64_t)n * kpad + k];
-    for (int sp = 1; sp < splits; ++sp) a += part[((int64_t)sp * npad + n) * kpad + k];
-    v = inv_levels * a;
-  }
-  dW[i] = v;
 }
 
 int64_t round64(int64_t v) { return (v + 63) / 64 * 64; }
@@ -337,8 +288,7 @@ bool conv_wgrad_geo(int64_t B, int64_t C, int64_t H, int64_t W, int64_t N, int k
 int64_t conv_wgrad_splits(const ConvGeo& g) {
   const int64_t tiles = (round64(g.N) / CW_TN) * (round64(g.K) / CW_TK);
   const int64_t nst = ((int64_t)g.M + CW_BM - 1) / CW_BM;
-  return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(CW_MAX_SPLITS, nst),
-                                                 (CW_TARGET_WAVES + tiles - 1) / tiles));
+  return split_count(tiles, nst, CW_MAX_SPLITS, CW_TARGET_WAVES);
 }
 
 }  // namespace
@@ -355,8 +305,7 @@ int qvit_ultra_weight_quant_backward(const float* w, const float* grad_out, int6
   if (!w || !grad_out || !grad_w || !workspace) return QVIT_ENULL;
   if (n < 0 || w_bit < 2 || w_bit > 8) return QVIT_EINVAL;   // quant_ultra.py:33 (1 and 32 are not this quantizer)
   if (workspace_bytes < qvit_ultra_weight_quant_backward_workspace_bytes(n)) return QVIT_EINVAL;
-  if ((((uintptr_t)w) | ((uintptr_t)grad_out) | ((uintptr_t)grad_w)) & 3) return QVIT_EALIGN;
-  if ((uintptr_t)workspace & 7) return QVIT_EALIGN;
+  if (qvit_misaligned(3, w, grad_out, grad_w) || qvit_misaligned(7, workspace)) return QVIT_EALIGN;
   if (n == 0) return QVIT_OK;
   const WqWorkspace ws = wq_workspace(workspace);
   const hipError_t e = hipMemsetAsync(ws.maxbits, 0, sizeof(unsigned), stream);
@@ -369,18 +318,18 @@ int qvit_ultra_weight_quant_backward(const float* w, const float* grad_out, int6
                      ws.coef);
   hipLaunchKernelGGL(ultra_wq_apply_kernel, dim3(grid), dim3(kThreads), 0, stream, w, grad_out, n, ws.maxbits,
                      ws.coef, grad_w);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int qvit_ultra_act_quant_backward(const float* x, const float* grad_out, int64_t n, float* grad_x,
                                   hipStream_t stream) {
   if (!x || !grad_out || !grad_x) return QVIT_ENULL;
   if (n < 0) return QVIT_EINVAL;
-  if ((((uintptr_t)x) | ((uintptr_t)grad_out) | ((uintptr_t)grad_x)) & 15) return QVIT_EALIGN;
+  if (qvit_misaligned(15, x, grad_out, grad_x)) return QVIT_EALIGN;
   if (n == 0) return QVIT_OK;
   hipLaunchKernelGGL(ultra_act_backward_kernel, dim3(stream_grid(n, kVec)), dim3(kThreads), 0, stream, x, grad_out,
                      n, grad_x);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int64_t qvit_conv_wgrad_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int64_t N, int kh, int kw,
@@ -397,23 +346,22 @@ int qvit_conv_wgrad(const float* G, const float* X, int64_t B, int64_t C, int64_
   ConvGeo g;
   if (!conv_wgrad_geo(B, C, H, W, N, kh, kw, sh, sw, ph, pw, dh, dw, &g)) return QVIT_EINVAL;
   if (levels < 1 || levels > 127) return QVIT_EINVAL;
-  if ((((uintptr_t)G) | ((uintptr_t)X) | ((uintptr_t)dW)) & 3) return QVIT_EALIGN;
-  if ((uintptr_t)workspace & 15) return QVIT_EALIGN;
+  if (qvit_misaligned(3, G, X, dW) || qvit_misaligned(15, workspace)) return QVIT_EALIGN;
   const int64_t npad = round64(g.N), kpad = round64(g.K);
   const int64_t splits = g.M == 0 ? 0 : conv_wgrad_splits(g);
   if (workspace_bytes < conv_wgrad_splits(g) * npad * kpad * 4) return QVIT_EINVAL;
   float* part = reinterpret_cast<float*>(workspace);
   if (splits > 0) {
     const int64_t total = splits * (npad / CW_TN) * (kpad / CW_TK);
-    const int gvec = ((int64_t)g.OH * g.OW) % 4 == 0 && (((uintptr_t)G) & 15) == 0;
+    const int gvec = ((int64_t)g.OH * g.OW) % 4 == 0 && !qvit_misaligned(15, G);
     hipLaunchKernelGGL(conv_wgrad_kernel, dim3((unsigned)((total + 3) / 4)), dim3(256), 0, stream, G, X, g,
                        (float)levels, (int)splits, (int)npad, (int)kpad, gvec, part);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return qvit_hip_status(e);
   }
-  hipLaunchKernelGGL(conv_wgrad_fold_kernel, dim3((unsigned)(((int64_t)g.N * g.K + 255) / 256)), dim3(256), 0,
+  hipLaunchKernelGGL(split_fold_kernel<float>, dim3((unsigned)(((int64_t)g.N * g.K + 255) / 256)), dim3(256), 0,
                      stream, part, (int)splits, g.N, g.K, (int)npad, (int)kpad, 1.f / (float)levels, dW);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 }  // extern "C"

@@ -21,12 +21,12 @@
 // elements of x (8 x 16 B per lane); every index inside a plane is int32, the plane's base int64. The 16-byte arm
 // runs when the pointers are 16-byte aligned (flags: 4) and H W % 4 == 0 (pooled: W % 4 == 0, a lane then owns two
 // adjacent windows: two float4 rows in, one float2 out); otherwise the scalar arm, same slices. Reductions:
-// per-thread double accumulation, quant_bwd_common.h's fixed-order wave / block tree, one partial pair per
+// per-thread double accumulation, reduce_common.h's fixed-order wave / block tree, one partial pair per
 // workgroup at [c][b][slice], one workgroup per channel folding its partials in index order. No atomics: two calls
 // give the same bits, whatever the workspace held.
 #include <initializer_list>
 
-#include "quant_bwd_common.h"
+#include "reduce_common.h"
 
 namespace {
 
@@ -39,8 +39,6 @@ struct BnGeo {
   double M;
 };
 
-inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
-
 // stats: always slices of the full plane; the other three: of the pooled plane when pool (2048 windows a slice)
 bool bn_geo(int64_t B, int64_t C, int64_t H, int64_t W, int pool, bool stats, BnGeo* g) {
   const int64_t lim = INT32_MAX;
@@ -51,7 +49,7 @@ bool bn_geo(int64_t B, int64_t C, int64_t H, int64_t W, int pool, bool stats, Bn
   if (B * HW < 2) return false;                         // batch statistics need two values per channel
   if (pool && (H < 2 || W < 2)) return false;           // an empty pooled map
   const int64_t OH = pool ? H / 2 : H, OW = pool ? W / 2 : W;
-  const int64_t S = (pool && !stats) ? cdiv64(OH * OW, kChunk / 4) : cdiv64(HW, kChunk);
+  const int64_t S = (pool && !stats) ? cdiv(OH * OW, kChunk / 4) : cdiv(HW, kChunk);
   if (B * C * S > lim) return false;                    // the grid
   *g = BnGeo{(int)B, (int)C, (int)H, (int)W, (int)HW, (int)OH, (int)OW, (int)(OH * OW), (int)S, pool,
              (double)B * (double)HW};
@@ -98,25 +96,10 @@ __global__ __launch_bounds__(kThreads) void bn_stats_partial_kernel(const float*
     for (int i = e0 + (int)threadIdx.x; i < e1; i += kThreads) stat_add(xp[i], K, s, ss);
   }
   block_sum3(s, ss, unused, lds);
-  if (threadIdx.x == 0) {
-    const int64_t j = partial_index(g, sl);
-    partials[2 * j] = s;
-    partials[2 * j + 1] = ss;
-  }
+  if (threadIdx.x == 0) store_partial2(partials, partial_index(g, sl), s, ss);
 }
 
-// one workgroup per channel: thread i adds the channel's partials i, i + 256, ... in that order, then the tree
-QVIT_DEV void fold_pairs(const double* __restrict__ p, int n, double& s0, double& s1, double (*lds)[3]) {
-  double unused = 0.0;
-  s0 = 0.0;
-  s1 = 0.0;
-  for (int j = threadIdx.x; j < n; j += kThreads) {
-    s0 += p[2 * (int64_t)j];
-    s1 += p[2 * (int64_t)j + 1];
-  }
-  block_sum3(s0, s1, unused, lds);
-}
-
+// one workgroup per channel folds the channel's partials (fold_partials2)
 __global__ __launch_bounds__(kThreads) void bn_stats_finish_kernel(const double* __restrict__ partials,
                                                                    const float* __restrict__ x, BnGeo g, double eps,
                                                                    double factor, float* rmean, float* rvar,
@@ -124,8 +107,8 @@ __global__ __launch_bounds__(kThreads) void bn_stats_finish_kernel(const double*
                                                                    float* __restrict__ invstd) {
   __shared__ double lds[kWaves][3];
   const int c = blockIdx.x, n = g.B * g.S;
-  double s, ss;
-  fold_pairs(partials + 2 * (int64_t)c * n, n, s, ss, lds);
+  double s = 0.0, ss = 0.0;
+  fold_partials2(partials + 2 * (int64_t)c * n, n, s, ss, lds);
   if (threadIdx.x == 0) {
     const double K = (double)x[(int64_t)c * g.HW];
     const double m = s / g.M;
@@ -294,11 +277,7 @@ __global__ __launch_bounds__(kThreads) void bn_act_reduce_kernel(const float* __
       if (flags[base + i] & 1) sums_add(go[base + i], x[base + i], k, s1, s2);
   }
   block_sum3(s1, s2, unused, lds);
-  if (threadIdx.x == 0) {
-    const int64_t j = partial_index(g, sl);
-    partials[2 * j] = s1;
-    partials[2 * j + 1] = s2;
-  }
+  if (threadIdx.x == 0) store_partial2(partials, partial_index(g, sl), s1, s2);
 }
 
 __global__ __launch_bounds__(kThreads) void bn_act_pool_reduce_kernel(const float* __restrict__ x,
@@ -338,19 +317,15 @@ __global__ __launch_bounds__(kThreads) void bn_act_pool_reduce_kernel(const floa
     }
   }
   block_sum3(s1, s2, unused, lds);
-  if (threadIdx.x == 0) {
-    const int64_t j = partial_index(g, sl);
-    partials[2 * j] = s1;
-    partials[2 * j + 1] = s2;
-  }
+  if (threadIdx.x == 0) store_partial2(partials, partial_index(g, sl), s1, s2);
 }
 
 __global__ __launch_bounds__(kThreads) void bn_bwd_finish_kernel(const double* __restrict__ partials, BnGeo g,
                                                                  double* __restrict__ sums) {
   __shared__ double lds[kWaves][3];
   const int c = blockIdx.x, n = g.B * g.S;
-  double s1, s2;
-  fold_pairs(partials + 2 * (int64_t)c * n, n, s1, s2, lds);
+  double s1 = 0.0, s2 = 0.0;
+  fold_partials2(partials + 2 * (int64_t)c * n, n, s1, s2, lds);
   if (threadIdx.x == 0) {
     sums[c] = s1;
     sums[g.C + c] = s2;
@@ -480,14 +455,12 @@ __global__ __launch_bounds__(kThreads) void bn_act_pool_dx_kernel(const float* _
   write_param_grads(sl, g, sums, dgamma, dbeta);
 }
 
-inline bool al(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
-
 // the 16-byte arm: every plane base 16-byte aligned in the fp32 tensors (4 in the flag bytes) and rows that pair up
 inline int vec_arm(const BnGeo& g, bool pooled_kernel, std::initializer_list<const void*> f32, const void* flags) {
   if (pooled_kernel ? (g.W % 4 != 0) : (g.HW % 4 != 0)) return 0;
   for (const void* p : f32)
-    if (!al(p, 16)) return 0;
-  return (!flags || al(flags, 4)) ? 1 : 0;
+    if (qvit_misaligned(15, p)) return 0;
+  return qvit_misaligned(3, flags) ? 0 : 1;
 }
 
 }  // namespace
@@ -507,8 +480,7 @@ int qvit_bn_stats(const float* x, int64_t B, int64_t C, int64_t H, int64_t W, do
   BnGeo g;
   if (!bn_geo(B, C, H, W, 0, true, &g)) return QVIT_EINVAL;
   if (!(eps >= 0.0) || workspace_bytes < qvit_bn_stats_workspace_bytes(B, C, H, W)) return QVIT_EINVAL;
-  if (!al(x, 4) || !al(mean, 4) || !al(var, 4) || !al(invstd, 4) || !al(running_mean, 4) || !al(running_var, 4) ||
-      !al(workspace, 8))
+  if (qvit_misaligned(3, x, mean, var, invstd, running_mean, running_var) || qvit_misaligned(7, workspace))
     return QVIT_EALIGN;
   double* partials = static_cast<double*>(workspace);
   const int vec = vec_arm(g, false, {x}, nullptr);
@@ -516,7 +488,7 @@ int qvit_bn_stats(const float* x, int64_t B, int64_t C, int64_t H, int64_t W, do
                      x, g, vec, partials);
   hipLaunchKernelGGL(bn_stats_finish_kernel, dim3((unsigned)g.C), dim3(kThreads), 0, stream, partials, x, g, eps,
                      factor, running_mean, running_var, mean, var, invstd);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int qvit_bn_act_pool_forward(const float* x, int64_t B, int64_t C, int64_t H, int64_t W, const float* mean,
@@ -526,7 +498,7 @@ int qvit_bn_act_pool_forward(const float* x, int64_t B, int64_t C, int64_t H, in
   BnGeo g;
   if (!bn_geo(B, C, H, W, pool, false, &g)) return QVIT_EINVAL;
   if (levels < 1 || levels > 127) return QVIT_EINVAL;
-  if (!al(x, 4) || !al(mean, 4) || !al(invstd, 4) || !al(gamma, 4) || !al(beta, 4) || !al(out, 4)) return QVIT_EALIGN;
+  if (qvit_misaligned(3, x, mean, invstd, gamma, beta, out)) return QVIT_EALIGN;
   const dim3 grid((unsigned)((int64_t)g.B * g.C * g.S));
   const int vec = vec_arm(g, pool != 0, {x, out}, flags);
   if (pool)
@@ -535,7 +507,7 @@ int qvit_bn_act_pool_forward(const float* x, int64_t B, int64_t C, int64_t H, in
   else
     hipLaunchKernelGGL(bn_act_forward_kernel, grid, dim3(kThreads), 0, stream, x, g, vec, mean, invstd, gamma, beta,
                        levels, out, flags);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int64_t qvit_bn_act_pool_backward_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int pool) {
@@ -552,8 +524,7 @@ int qvit_bn_act_pool_backward_reduce(const float* x, const float* grad_out, cons
   BnGeo g;
   if (!bn_geo(B, C, H, W, pool, false, &g)) return QVIT_EINVAL;
   if (workspace_bytes < qvit_bn_act_pool_backward_workspace_bytes(B, C, H, W, pool)) return QVIT_EINVAL;
-  if (!al(x, 4) || !al(grad_out, 4) || !al(mean, 4) || !al(invstd, 4) || !al(sums, 8) || !al(workspace, 8))
-    return QVIT_EALIGN;
+  if (qvit_misaligned(3, x, grad_out, mean, invstd) || qvit_misaligned(7, sums, workspace)) return QVIT_EALIGN;
   double* partials = static_cast<double*>(workspace);
   const dim3 grid((unsigned)((int64_t)g.B * g.C * g.S));
   const int vec = vec_arm(g, pool != 0, {x, grad_out}, flags);
@@ -564,7 +535,7 @@ int qvit_bn_act_pool_backward_reduce(const float* x, const float* grad_out, cons
     hipLaunchKernelGGL(bn_act_reduce_kernel, grid, dim3(kThreads), 0, stream, x, grad_out, flags, g, vec, mean,
                        invstd, partials);
   hipLaunchKernelGGL(bn_bwd_finish_kernel, dim3((unsigned)g.C), dim3(kThreads), 0, stream, partials, g, sums);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 int qvit_bn_act_pool_backward_dx(const float* x, const float* grad_out, const uint8_t* flags, int64_t B, int64_t C,
@@ -574,8 +545,7 @@ int qvit_bn_act_pool_backward_dx(const float* x, const float* grad_out, const ui
   if (!x || !grad_out || !flags || !mean || !invstd || !sums || !dx) return QVIT_ENULL;
   BnGeo g;
   if (!bn_geo(B, C, H, W, pool, false, &g)) return QVIT_EINVAL;
-  if (!al(x, 4) || !al(grad_out, 4) || !al(mean, 4) || !al(invstd, 4) || !al(gamma, 4) || !al(sums, 8) ||
-      !al(dx, 4) || !al(dgamma, 4) || !al(dbeta, 4))
+  if (qvit_misaligned(3, x, grad_out, mean, invstd, gamma, dx, dgamma, dbeta) || qvit_misaligned(7, sums))
     return QVIT_EALIGN;
   const dim3 grid((unsigned)((int64_t)g.B * g.C * g.S));
   const int vec = vec_arm(g, pool != 0, {x, grad_out, dx}, flags);
@@ -585,7 +555,7 @@ int qvit_bn_act_pool_backward_dx(const float* x, const float* grad_out, const ui
   else
     hipLaunchKernelGGL(bn_act_dx_kernel, grid, dim3(kThreads), 0, stream, x, grad_out, flags, g, vec, mean, invstd,
                        gamma, sums, dx, dgamma, dbeta);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 }  // extern "C"

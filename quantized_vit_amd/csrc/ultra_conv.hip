@@ -1051,18 +1051,18 @@ int launch_conv(const int8_t* in, int B, int H, int W, const int8_t* w, int kpad
   // (CIN 64: two halo buffers and the weights leave room for one workgroup per CU; that layer keeps the
   // synchronous halo at two workgroups)
   const bool stg = CIN <= 32 && POOL != 0 && OUT != 1 && cout_real == COUT && (ldo % 16) == 0 &&
-                   (((uintptr_t)out) & 15) == 0 &&
+                   !qvit_misaligned(15, out) &&
                    (int64_t)(H / 2) * (W / 2) * ldo < ((int64_t)1 << 31);
   if constexpr (CIN <= 32 && POOL != 0 && OUT != 1) {
     if (stg) {
       hipLaunchKernelGGL((ultra_conv_kernel<CIN, KS, COUT, POOL, OUT, true>), dim3(grid), dim3(256), 0, stream, in, B,
                          H, W, w, kpad, den, alpha, shift, levels, cout_real, out, ldo, sbits);
-      return qvit_hip_status(hipGetLastError());
+      return qvit_launch_status();
     }
   }
     hipLaunchKernelGGL((ultra_conv_kernel<CIN, KS, COUT, POOL, OUT, false>), dim3(grid), dim3(256), 0, stream, in, B,
                        H, W, w, kpad, den, alpha, shift, levels, cout_real, out, ldo, sbits);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 }  // namespace
@@ -1081,7 +1081,7 @@ extern "C" int qvit_ultra_weight_codes(const float* w, int64_t cout, int64_t cin
   hipLaunchKernelGGL(ultra_wcodes_kernel, dim3(grid_cap(cout_pad * kpad)), dim3(256), 0, stream, w, (int)cout,
                      (int)cin, (int)ks, workspace, (float)((1 << (w_bit - 1)) - 1), codes, (int)kpad, (int)cout_pad,
                      values);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 extern "C" int qvit_ultra_bn_fold(const float* gamma, const float* beta, const float* mean, const float* var,
@@ -1090,21 +1090,21 @@ extern "C" int qvit_ultra_bn_fold(const float* gamma, const float* beta, const f
   if (n <= 0 || n > (1 << 20)) return QVIT_EINVAL;
   hipLaunchKernelGGL(ultra_bn_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, gamma, beta, mean,
                      var, eps, (int)n, alpha, shift);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 extern "C" int qvit_ultra_conv0(const float* img, int64_t B, int64_t H, int64_t W, const float* wvals,
                                 const float* alpha, const float* shift, int a_bit, int8_t* out, hipStream_t stream) {
   if (!img || !wvals || !alpha || !shift || !out) return QVIT_ENULL;
   if (B < 0 || H < 2 || W < 2 || a_bit < 1 || a_bit > 7) return QVIT_EINVAL;
-  if ((((uintptr_t)out) & 15)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, out)) return QVIT_EALIGN;
   if (B * H * W > INT32_MAX) return QVIT_EINVAL;
   if (B == 0) return QVIT_OK;
   // persistent over 16 x 32 tiles
   const int64_t ntiles = B * ((H + C0_TY - 1) / C0_TY) * ((W + C0_TX - 1) / C0_TX);
   if (ntiles > INT32_MAX) return QVIT_EINVAL;
   const float levels = (float)((1 << a_bit) - 1);
-  if ((W % 4) == 0 && (((uintptr_t)img) & 15) == 0) {  // 16-B quad loads
+  if ((W % 4) == 0 && !qvit_misaligned(15, img)) {  // 16-B quad loads
     const int64_t grid = resident_grid(ultra_conv0_mfma_kernel<true>, ntiles);
     hipLaunchKernelGGL(ultra_conv0_mfma_kernel<true>, dim3((unsigned)grid), dim3(256), 0, stream, img, (int)B, (int)H,
                        (int)W, wvals, alpha, shift, levels, out);
@@ -1113,7 +1113,7 @@ extern "C" int qvit_ultra_conv0(const float* img, int64_t B, int64_t H, int64_t 
     hipLaunchKernelGGL(ultra_conv0_mfma_kernel<false>, dim3((unsigned)grid), dim3(256), 0, stream, img, (int)B, (int)H,
                        (int)W, wvals, alpha, shift, levels, out);
   }
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 extern "C" int qvit_ultra_conv(const int8_t* in, int64_t B, int64_t H, int64_t W, int64_t cin, int64_t ks,
@@ -1126,8 +1126,8 @@ extern "C" int qvit_ultra_conv(const int8_t* in, int64_t B, int64_t H, int64_t W
   if (mode != QVIT_ULTRA_CODES && mode != QVIT_ULTRA_CODES_POOL && mode != QVIT_ULTRA_F32) return QVIT_EINVAL;
   if (mode != QVIT_ULTRA_F32 && !alpha) return QVIT_ENULL;
   if (mode == QVIT_ULTRA_CODES_POOL && ((H | W) & 1)) return QVIT_EINVAL;
-  if ((((uintptr_t)in) & 15) || (((uintptr_t)wcodes) & 15) || (kpad % 16)) return QVIT_EALIGN;
-  if (mode != QVIT_ULTRA_F32 && (ldo % 4 || (((uintptr_t)out) & 3) || cout % 4)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, in, wcodes) || (kpad % 16)) return QVIT_EALIGN;
+  if (mode != QVIT_ULTRA_F32 && (ldo % 4 || qvit_misaligned(3, out) || cout % 4)) return QVIT_EALIGN;
   if (B * H * W > INT32_MAX) return QVIT_EINVAL;
   if (B == 0) return QVIT_OK;
   const float den = (float)(((1 << (w_bit - 1)) - 1) * ((1 << a_bit) - 1));
@@ -1164,9 +1164,8 @@ extern "C" int qvit_ultra_tail(const int8_t* in, int64_t B, int64_t H, int64_t W
     return QVIT_EINVAL;
   if (kpad < 9 * 64 || hkpad < 64 || w_bit < 2 || w_bit > 8 || a_bit < 1 || a_bit > 7) return QVIT_EINVAL;
   if (B > INT32_MAX) return QVIT_EINVAL;
-  if ((((uintptr_t)in) & 15) || (kpad % 16) || (hkpad % 16) || (((uintptr_t)hcodes) & 15)) return QVIT_EALIGN;
-  for (int l = 0; l < 4; ++l)
-    if (((uintptr_t)wcodes[l]) & 15) return QVIT_EALIGN;
+  if (qvit_misaligned(15, in, hcodes) || (kpad % 16) || (hkpad % 16)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, wcodes[0], wcodes[1], wcodes[2], wcodes[3])) return QVIT_EALIGN;
   if (B == 0) return QVIT_OK;
   TailArgs ta;
   for (int l = 0; l < 4; ++l) {
@@ -1183,7 +1182,7 @@ extern "C" int qvit_ultra_tail(const int8_t* in, int64_t B, int64_t H, int64_t W
   else
     hipLaunchKernelGGL(ultra_tail_kernel<false>, dim3((unsigned)B), dim3(512), 0, stream, in, (int)H, (int)W, ta,
                        (int)kpad, hcodes, (int)hkpad, hbias, (int)hout, den, lv, out, (int)ldo, td);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 extern "C" int qvit_ultra_conv0_int(const uint8_t* img, int64_t B, int64_t H, int64_t W, const int8_t* wcodes,
@@ -1191,12 +1190,12 @@ extern "C" int qvit_ultra_conv0_int(const uint8_t* img, int64_t B, int64_t H, in
                                     hipStream_t stream) {
   if (!img || !wcodes || !inc || !bias || !out) return QVIT_ENULL;
   if (B < 0 || H < 2 || W < 2 || shift_bits < 1 || shift_bits > 40 || out_bit < 1 || out_bit > 7) return QVIT_EINVAL;
-  if ((((uintptr_t)out) & 15)) return QVIT_EALIGN;
+  if (qvit_misaligned(15, out)) return QVIT_EALIGN;
   if (B * H * W > INT32_MAX) return QVIT_EINVAL;
   if (B == 0) return QVIT_OK;
   const int64_t ntiles = B * ((H + C0_TY - 1) / C0_TY) * ((W + C0_TX - 1) / C0_TX);
   if (ntiles > INT32_MAX) return QVIT_EINVAL;
-  if ((W % 4) == 0 && (((uintptr_t)img) & 3) == 0) {  // 4-B quad loads
+  if ((W % 4) == 0 && !qvit_misaligned(3, img)) {  // 4-B quad loads
     const int64_t grid = resident_grid(ultra_conv0_int_mfma_kernel<true>, ntiles);
     hipLaunchKernelGGL(ultra_conv0_int_mfma_kernel<true>, dim3((unsigned)grid), dim3(256), 0, stream, img, (int)B,
                        (int)H, (int)W, wcodes, inc, bias, shift_bits, (1 << out_bit) - 1, out);
@@ -1205,7 +1204,7 @@ extern "C" int qvit_ultra_conv0_int(const uint8_t* img, int64_t B, int64_t H, in
     hipLaunchKernelGGL(ultra_conv0_int_mfma_kernel<false>, dim3((unsigned)grid), dim3(256), 0, stream, img, (int)B,
                        (int)H, (int)W, wcodes, inc, bias, shift_bits, (1 << out_bit) - 1, out);
   }
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
 
 extern "C" int qvit_ultra_conv_int(const int8_t* in, int64_t B, int64_t H, int64_t W, int64_t cin, int64_t ks,
@@ -1217,9 +1216,8 @@ extern "C" int qvit_ultra_conv_int(const int8_t* in, int64_t B, int64_t H, int64
       out_bit > 7)
     return QVIT_EINVAL;
   if (pool && ((H | W) & 1)) return QVIT_EINVAL;
-  if ((((uintptr_t)in) & 15) || (((uintptr_t)wcodes) & 15) || (kpad % 16)) return QVIT_EALIGN;
-  if (ldo % 4 || (((uintptr_t)out) & 3) || cout % 4 || (((uintptr_t)inc) & 3) || (((uintptr_t)bias) & 3))
-    return QVIT_EALIGN;
+  if (qvit_misaligned(15, in, wcodes) || (kpad % 16)) return QVIT_EALIGN;
+  if (ldo % 4 || cout % 4 || qvit_misaligned(3, out, inc, bias)) return QVIT_EALIGN;
   if (B * H * W > INT32_MAX) return QVIT_EINVAL;
   if (B == 0) return QVIT_OK;
   const float lv = (float)((1 << out_bit) - 1);
@@ -1248,5 +1246,5 @@ extern "C" int qvit_yolo_decode(const float* head, int64_t B, int64_t ny, int64_
   if (B == 0) return QVIT_OK;
   hipLaunchKernelGGL(yolo_decode_kernel, dim3(grid_cap(B * na * ny * nx * no)), dim3(256), 0, stream, head, (int)B,
                      (int)ny, (int)nx, (int)na, (int)no, (int)ldh, anchors, stride, io, p);
-  return qvit_hip_status(hipGetLastError());
+  return qvit_launch_status();
 }
