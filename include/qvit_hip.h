@@ -272,6 +272,8 @@ int qvit_pad_bias(const float* bias, int64_t n, float* out, int64_t npad, hipStr
  *   codes  : int8 [B*OH*OW][ldc], row (b, oh, ow), column (c, ih, iw) = c*kh*kw + ih*kw + iw;
  *            columns [C*kh*kw, kpad) zero. Zero-padding of the image quantizes to code 0, as in
  *            the reference (quantize_act runs before F.conv2d pads).
+ *   OH = (H + 2 ph - dh (kh - 1) - 1) / sh + 1, OW alike; a padded image smaller than the dilated kernel on
+ *   either axis is QVIT_EINVAL at every stride.
  */
 int qvit_im2col_quant_i8(const float* x, int64_t B, int64_t C, int64_t H, int64_t W,
                          int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,

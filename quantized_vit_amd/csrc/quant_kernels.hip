@@ -514,10 +514,13 @@ int qvit_im2col_quant_i8(const float* x, int64_t B, int64_t C, int64_t H, int64_
   if (B < 0 || C <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || ph < 0 ||
       pw < 0 || dh <= 0 || dw <= 0)
     return QVIT_EINVAL;
-  const int64_t OH = (H + 2 * ph - (int64_t)dh * (kh - 1) - 1) / sh + 1;
-  const int64_t OW = (W + 2 * pw - (int64_t)dw * (kw - 1) - 1) / sw + 1;
+  // the padded image has to hold the dilated kernel: checked on the extents, because the division below truncates
+  // toward zero and would turn an extent of -1 at a stride of 2 into one output
+  const int64_t eh = H + 2 * (int64_t)ph - (int64_t)dh * (kh - 1) - 1, ew = W + 2 * (int64_t)pw - (int64_t)dw * (kw - 1) - 1;
+  if (eh < 0 || ew < 0) return QVIT_EINVAL;
+  const int64_t OH = eh / sh + 1, OW = ew / sw + 1;
   const int64_t K = C * kh * kw;
-  if (OH <= 0 || OW <= 0 || kpad < K || kpad % 16 || ldc < kpad) return QVIT_EINVAL;
+  if (kpad < K || kpad % 16 || ldc < kpad) return QVIT_EINVAL;
   if ((ldc % 16) || qvit_misaligned(15, codes)) return QVIT_EALIGN;
   if (B == 0) return QVIT_OK;
   const int64_t work = B * OH * OW * (kpad / 16);

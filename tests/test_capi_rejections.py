@@ -83,9 +83,12 @@ PACK_WEIGHT = [
 
 
 def im2col(lib, x=A0, B=1, C=3, H=8, W=8, k=3, s=1, p=1, dil=1, qtype=LIN, d=A1, qm=A2, t=None, levels=0, codes=A3,
-           ldc=32, kpad=32):
-    return lib.qvit_im2col_quant_i8(_p(x), B, C, H, W, k, k, s, s, p, p, dil, dil, qtype, _p(d), _p(qm), _p(t), levels,
-                                    _p(codes), ldc, kpad, None)
+           ldc=32, kpad=32, kh=None, kw=None, sh=None, sw=None, ph=None, pw=None, dh=None, dw=None):
+    """k, s, p, dil go to both axes; kh .. dw override one axis each."""
+    ax = lambda one, both: both if one is None else one
+    return lib.qvit_im2col_quant_i8(_p(x), B, C, H, W, ax(kh, k), ax(kw, k), ax(sh, s), ax(sw, s), ax(ph, p), ax(pw, p),
+                                    ax(dh, dil), ax(dw, dil), qtype, _p(d), _p(qm), _p(t), levels, _p(codes), ldc, kpad,
+                                    None)
 
 
 IM2COL = [
@@ -96,6 +99,16 @@ IM2COL = [
     (dict(s=0), EINVAL), (dict(kpad=16), EINVAL), (dict(H=1, W=1, p=0), EINVAL),
     (dict(codes=A3 + 4), EALIGN), (dict(ldc=40), EALIGN), (dict(kpad=16, codes=A3 + 4), EINVAL),
     (dict(qtype=7, codes=A3 + 4), EINVAL),
+    # one axis bad, the other valid
+    (dict(kh=0), EINVAL), (dict(kw=0), EINVAL), (dict(sh=0), EINVAL), (dict(sw=0), EINVAL),
+    (dict(ph=-1), EINVAL), (dict(pw=-1), EINVAL), (dict(dh=0), EINVAL), (dict(dw=0), EINVAL),
+    (dict(W=1, pw=0), EINVAL), (dict(H=1, ph=0), EINVAL),                  # OH > 0, OW <= 0 and the reverse
+    (dict(W=2, pw=0, sw=2), EINVAL), (dict(H=2, ph=0, sh=2), EINVAL),      # a kernel one past the image, stride 2
+    # each argument reaches its own axis: valid as given, no output with the pair swapped
+    (dict(B=0, H=3, W=19, kh=1, kw=7, p=0), OK), (dict(H=3, W=19, kh=7, kw=1, p=0), EINVAL),
+    (dict(B=0, H=3, W=19, kh=1, kw=3, p=0, dw=9), OK), (dict(H=3, W=19, kh=3, kw=1, p=0, dh=9), EINVAL),
+    (dict(B=0, C=1, H=3, W=19, k=5, ph=1, pw=0), OK), (dict(C=1, H=3, W=19, k=5, ph=0, pw=1), EINVAL),
+    (dict(B=0, C=1, H=13, W=22, kh=2, kw=5, sh=2, sw=3, ph=3, pw=1, dh=3, dw=2), OK),
 ]
 
 

@@ -19,6 +19,12 @@ pytestmark = pytest.mark.gpu
 
 CLIP = (-2.0, 2.0)
 M, K_IN, N_OUT = 10, 64, 48
+# conv geometry: (kernel, stride, padding, dilation, input shape), 3 -> 8 channels
+CONV_SQUARE = (3, 1, 1, 1, (2, 3, 8, 8))
+# every pair differs between the axes, on a non-square image
+CONV_ASYM = ((2, 3), (2, 1), (1, 2), (1, 2), (2, 3, 9, 10))
+# the same without padding on the rows: OH = 4 and the last input row (8) is read by no output
+CONV_ASYM_UNREAD_ROW = ((2, 3), (2, 1), (0, 2), (1, 2), (2, 3, 9, 10))
 
 
 def _level_d(kind, q_m, t, level):
@@ -47,14 +53,14 @@ def _set(p, v):
         p.data.fill_(v)
 
 
-def _build(dev, kind, path, conv=False, seed=0):
+def _build(dev, kind, path, conv=False, seed=0, geom=CONV_SQUARE):
     from quantized_vit_amd.quant_layers import QuantizationMode, QuantizationType, QuantizeConv2d, QuantizeLinear
     mode, wq, aq = _case(kind, path)
     qt = QuantizationType.SYMMETRIC_LINEAR if kind == R.LINEAR else QuantizationType.SYMMETRIC_NONLINEAR
     qm = QuantizationMode.WEIGHT_AND_ACTIVATION if mode == "wa" else QuantizationMode.WEIGHT_ONLY
     if conv:
-        layer = QuantizeConv2d(3, 8, 3, stride=1, padding=1, bias=True, quant_type=qt, quant_mode=qm)
-        xshape = (2, 3, 8, 8)
+        k, s, p, dil, xshape = geom
+        layer = QuantizeConv2d(3, 8, k, stride=s, padding=p, dilation=dil, bias=True, quant_type=qt, quant_mode=qm)
     else:
         layer = QuantizeLinear(K_IN, N_OUT, bias=True, quant_type=qt, quant_mode=qm)
         xshape = (M, K_IN)
@@ -76,7 +82,7 @@ def _build(dev, kind, path, conv=False, seed=0):
     return layer, x, W, b, wq, aq
 
 
-def _reference(kind, x, W, b, wq, aq, Gw, conv):
+def _reference(kind, x, W, b, wq, aq, Gw, conv, geom=CONV_SQUARE):
     """The float64 CPU graph. Returns the leaves (with .grad) and the grad_out each quantizer saw."""
     leaf = lambda v: None if v is None else torch.tensor([float(np.float32(v))], dtype=torch.float64,
                                                          requires_grad=True)
@@ -86,14 +92,26 @@ def _reference(kind, x, W, b, wq, aq, Gw, conv):
     rec_w, rec_a = {}, {}
     xq = R.RefQuantizer.apply(xr, pa[0], pa[1], pa[2], kind, CLIP, rec_a) if aq is not None else xr
     wq_ = R.RefQuantizer.apply(Wr, pw[0], pw[1], pw[2], kind, CLIP, rec_w)
-    y = F.conv2d(xq, wq_, br, 1, 1) if conv else F.linear(xq, wq_, br)
+    y = F.conv2d(xq, wq_, br, *geom[1:4]) if conv else F.linear(xq, wq_, br)
     (y * Gw.double()).sum().backward()
     return dict(x=xr, W=Wr, b=br, pw=pw, pa=pa, rec_w=rec_w, rec_a=rec_a, xq=xq.detach(), wq=wq_.detach(), y=y.detach())
 
 
-def _check_layer(dev, kind, path, conv=False):
+def _unread_rows_cols(geom):
+    """Input rows and columns that no output position reads (from the index arithmetic of the convolution)."""
+    pair = lambda v: (v, v) if isinstance(v, int) else tuple(v)
+    k, s, p, dil = (pair(v) for v in geom[:4])
+    out = []
+    for ax, size in enumerate(geom[4][2:]):
+        n_out = (size + 2 * p[ax] - dil[ax] * (k[ax] - 1) - 1) // s[ax] + 1
+        read = {o * s[ax] - p[ax] + i * dil[ax] for o in range(n_out) for i in range(k[ax])}
+        out.append([j for j in range(size) if j not in read])
+    return out
+
+
+def _check_layer(dev, kind, path, conv=False, geom=CONV_SQUARE):
     from quantized_vit_amd import quant_layers as ql
-    layer, x, W, b, wq, aq = _build(dev, kind, path, conv)
+    layer, x, W, b, wq, aq = _build(dev, kind, path, conv, geom=geom)
     plan = layer.quant_plan()
     if path == "int":
         assert plan.int_path
@@ -115,16 +133,16 @@ def _check_layer(dev, kind, path, conv=False):
     Gw = torch.randn(y.shape, generator=gen)
     (y * Gw.to(dev)).sum().backward()
 
-    ref = _reference(kind, x, W, b, wq, aq, Gw, conv)
+    ref = _reference(kind, x, W, b, wq, aq, Gw, conv, geom)
     assert torch.allclose(y0.cpu().double(), ref["y"], rtol=1e-4, atol=1e-5)   # both sides quantized alike
     G = Gw.double()
     u = 2.0 ** -24
     if conv:
         rows = G.shape[0] * G.shape[2] * G.shape[3]
         b_bound = 4 * rows * u * G.abs().sum((0, 2, 3))
-        w_bound = 4 * rows * u * torch.nn.grad.conv2d_weight(ref["xq"].abs(), tuple(W.shape), G.abs(), 1, 1)
+        w_bound = 4 * rows * u * torch.nn.grad.conv2d_weight(ref["xq"].abs(), tuple(W.shape), G.abs(), *geom[1:4])
         kx = W.shape[0] * W.shape[2] * W.shape[3]
-        x_bound = 4 * kx * u * torch.nn.grad.conv2d_input(tuple(x.shape), ref["wq"].abs(), G.abs(), 1, 1)
+        x_bound = 4 * kx * u * torch.nn.grad.conv2d_input(tuple(x.shape), ref["wq"].abs(), G.abs(), *geom[1:4])
     else:
         rows = G.shape[0]
         b_bound = 4 * rows * u * G.abs().sum(0)
@@ -142,6 +160,10 @@ def _check_layer(dev, kind, path, conv=False):
     close("bias.grad", layer.bias.grad, ref["b"].grad, b_bound)
     close("weight.grad", layer.weight.grad, ref["W"].grad, w_bound)
     close("input.grad", xd.grad, ref["x"].grad, x_bound)
+    if conv:   # what no output reads has no gradient at all
+        unread_rows, unread_cols = _unread_rows_cols(geom)
+        assert not bool(xd.grad[:, :, unread_rows, :].any()) and not bool(ref["x"].grad[:, :, unread_rows, :].any())
+        assert not bool(xd.grad[:, :, :, unread_cols].any()) and not bool(ref["x"].grad[:, :, :, unread_cols].any())
 
     def scalars(which, values, params, leaves, rec):
         _, _, floor, bounds = R.sum_bounds(values.reshape(-1), rec["grad_out"].reshape(-1).float(), kind, *params,
@@ -170,6 +192,16 @@ def test_linear_backward(dev, kind, path):
 @pytest.mark.parametrize("kind", [R.LINEAR, R.NONLINEAR])
 def test_conv_backward(dev, kind):
     _check_layer(dev, kind, "int", conv=True)
+
+
+@pytest.mark.parametrize("geom", [CONV_ASYM, CONV_ASYM_UNREAD_ROW], ids=["asym", "asym-unread-row"])
+@pytest.mark.parametrize("kind", [R.LINEAR, R.NONLINEAR])
+def test_conv_backward_geometry(dev, kind, geom):
+    """Per-axis kernel, stride, padding and dilation on a 9 x 10 image. CONV_ASYM reads every input row (with a
+    row padding of 1 the last output row reaches input row 8); CONV_ASYM_UNREAD_ROW leaves row 8 unread, and its
+    gradient has to be exactly zero."""
+    assert _unread_rows_cols(CONV_ASYM) == [[], []] and _unread_rows_cols(CONV_ASYM_UNREAD_ROW) == [[8], []]
+    _check_layer(dev, kind, "int", conv=True, geom=geom)
 
 
 def test_requires_grad_false_leaves_none(dev):
