@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -594,6 +594,13 @@ def gemm_wgrad(G: torch.Tensor, codes: torch.Tensor, K: int, d_act: torch.Tensor
     return out
 
 
+def conv_out_hw(H: int, W: int, kernel_size, stride, padding, dilation) -> Tuple[int, int]:
+    """(OH, OW) of a convolution on an H x W image, as torch and qvit_common.h's qvit_conv_shape count them. (A
+    padded image smaller than the dilated kernel is the library's to reject: it checks the extents itself.)"""
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = kernel_size, stride, padding, dilation
+    return (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+
+
 def conv_wonly(x: torch.Tensor, kernel_size, stride, padding, dilation, packed: torch.Tensor, wfmt: int, N: int,
                npad: int, kpad: int, d_wt: torch.Tensor, bias_pad: Optional[torch.Tensor],
                split: bool = True) -> torch.Tensor:
@@ -605,8 +612,7 @@ def conv_wonly(x: torch.Tensor, kernel_size, stride, padding, dilation, packed: 
         x = x.float().contiguous()
     B, C, H, W = x.shape
     (kh, kw), (sh, sw), (ph, pw), (dh, dw) = kernel_size, stride, padding, dilation
-    OH = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    OW = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    OH, OW = conv_out_hw(H, W, kernel_size, stride, padding, dilation)
     y = torch.empty((B, N, OH, OW), dtype=torch.float32, device=x.device)
     M = B * OH * OW
     small = split and (npad // 256) * ((M + 63) // 64) < 128 and not narrow_conv_fits(wfmt, N, C * kh * kw, H, W)
@@ -631,8 +637,7 @@ def conv_wonly_bn_act(x: torch.Tensor, kernel_size, stride, padding, dilation, p
     if x.dtype != torch.float32 or not x.is_contiguous():
         x = x.float().contiguous()
     B, C, H, W = x.shape
-    OH = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    OW = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    OH, OW = conv_out_hw(H, W, kernel_size, stride, padding, dilation)
     y = torch.empty((B, N, OH, OW), dtype=torch.float32, device=x.device)
     _check(load().qvit_conv_wonly_bn_act(_ptr(x), B, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw, _ptr(packed), wfmt, N,
                                        npad, kpad, _ptr(d_wt), _ptr(bias_pad), _ptr(bn_alpha), _ptr(bn_shift),
@@ -986,8 +991,7 @@ def conv_wgrad(G: torch.Tensor, x: torch.Tensor, kernel_size, stride, padding, d
     B, C, H, W = x.shape
     N = G.shape[1]
     (kh, kw), (sh, sw), (ph, pw), (dh, dw) = kernel_size, stride, padding, dilation
-    OH = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-    OW = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+    OH, OW = conv_out_hw(H, W, kernel_size, stride, padding, dilation)
     if tuple(G.shape) != (B, N, OH, OW):
         raise QvitError(f"conv_wgrad: grad_out {tuple(G.shape)} for an output of {(B, N, OH, OW)}")
     if out is None:

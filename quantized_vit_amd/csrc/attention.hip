@@ -443,14 +443,7 @@ extern "C" int qvit_attention_split(const void* qkv_hi, const void* qkv_lo, int6
   if (nblk > INT32_MAX) return QVIT_EINVAL;
   const _Float16* hi = reinterpret_cast<const _Float16*>(qkv_hi);
   const _Float16* lo = reinterpret_cast<const _Float16*>(qkv_lo);
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  const int64_t grid = std::min<int64_t>(nblk, 2 * (int64_t)cus);  // two resident workgroups per CU
+  const int64_t grid = std::min<int64_t>(nblk, 2 * (int64_t)qvit_device_cus());  // two resident workgroups per CU
   if (out_mode == QVIT_ATT_F32)
     hipLaunchKernelGGL(attn_split_kernel<0>, dim3((unsigned)grid), dim3(256), 0, stream, hi, lo, (int)N, (int)H,
                        (int)nblk, scale, in_scale, out, ldo, out_qtype, out_d, out_qm, out_t, out_levels,

@@ -1131,17 +1131,6 @@ __global__ __launch_bounds__((Geo<WFMT, WM>::NT), (Geo<WFMT, WM>::MIN_BLOCKS)) v
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
-int device_cus() {
-  static int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  return cus;
-}
-
 #ifndef QVIT_GEMM_L2
 #define QVIT_GEMM_L2 1
 #endif
@@ -1163,7 +1152,7 @@ int launch(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, i
     const int64_t mc = (M - m0 < rows) ? M - m0 : rows;
     const int64_t ntiles = (npad / BN) * ((mc + G::BM - 1) / G::BM);
     // resident blocks, a multiple of 8 (one team per XCD), no more than the tiles need
-    int64_t grid = (int64_t)device_cus() * G::MIN_BLOCKS / 8 * 8;
+    int64_t grid = (int64_t)qvit_device_cus() * G::MIN_BLOCKS / 8 * 8;
     const int64_t need = (ntiles + 7) / 8 * 8;
     if (grid > need) grid = need;
     if (grid < 8) grid = 8;

@@ -537,18 +537,11 @@ template <int EPI>
 int narrow_launch(const NarrowGeo& g, const float* X, int64_t M, const int8_t* w, int wfmt, int64_t N,
                   const float* d_wt, const float* bias, const float* bn_a, const float* bn_s, float levels, float* Y,
                   const WoConv& cg, hipStream_t stream) {
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
   // wave units of 16 (PAIR: 32) pixels; resident workgroups (8 per CU), no more than the units need
   const bool pair = cg.kreal <= 32;
   const int64_t wtiles = (M + (pair ? 31 : 15)) / (pair ? 32 : 16);
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((wtiles + NW_WAVES - 1) / NW_WAVES,
-                                                                         8 * (int64_t)cus));
+                                                                         8 * (int64_t)qvit_device_cus()));
 #define QVIT_NW2(F, T, PR)                                                                                        \
   hipLaunchKernelGGL((conv_wonly_narrow_kernel<F, T, EPI, PR>), dim3(grid), dim3(NW_WAVES * 64), 0, stream, X,      \
                      (int)M, g.nke, w, (int)N, d_wt, bias, bn_a, bn_s, levels, Y, cg)
@@ -645,21 +638,18 @@ int conv_args(const float* X, int64_t B, int64_t C, int64_t H, int64_t W, int kh
               const float* bias, float* Y, WoConv& cg, int64_t& M) {
   if (!X || !Wp || !Y || !d_wt) return QVIT_ENULL;
   if (wfmt != QVIT_W4 && wfmt != QVIT_W8 && wfmt != QVIT_W16 && wfmt != QVIT_W24) return QVIT_EINVAL;
-  if (B < 0 || C <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || ph < 0 || pw < 0 ||
-      dh <= 0 || dw <= 0)
-    return QVIT_EINVAL;
+  // (the upper bounds first: they bound what qvit_conv_shape multiplies; a size below its range passes them and fails
+  // there, with the same status)
   if (C > INT32_MAX || H > INT32_MAX || W > INT32_MAX || B * C * H * W > (int64_t)1 << 40) return QVIT_EINVAL;
-  const int64_t OH = (H + 2 * ph - (int64_t)dh * (kh - 1) - 1) / sh + 1;
-  const int64_t OW = (W + 2 * pw - (int64_t)dw * (kw - 1) - 1) / sw + 1;
-  const int64_t kreal = C * kh * kw;
-  if (H + 2 * ph < (int64_t)dh * (kh - 1) + 1 || W + 2 * pw < (int64_t)dw * (kw - 1) + 1) return QVIT_EINVAL;
-  if (K <= 0 || K % QVIT_TILE_K || K < kreal || K > (1 << 24) || N <= 0 || npad < N || npad % WO_BN ||
+  ConvShape cs;
+  if (qvit_conv_shape(B, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw, cs)) return QVIT_EINVAL;
+  if (K <= 0 || K % QVIT_TILE_K || K < cs.K || K > (1 << 24) || N <= 0 || npad < N || npad % WO_BN ||
       npad > INT32_MAX / 2)
     return QVIT_EINVAL;
-  M = B * OH * OW;
-  if (M > INT32_MAX / 2 || OH * OW > INT32_MAX / 2) return QVIT_EINVAL;
+  M = cs.M;
+  if (M > INT32_MAX / 2 || cs.OH * cs.OW > INT32_MAX / 2) return QVIT_EINVAL;
   if (qvit_misaligned(15, Wp, bias)) return QVIT_EALIGN;
-  cg = WoConv{(int)C, (int)H, (int)W, kh, kw, sh, sw, ph, pw, dh, dw, (int)OW, (int)(OH * OW), (int)kreal};
+  cg = WoConv{(int)C, (int)H, (int)W, kh, kw, sh, sw, ph, pw, dh, dw, (int)cs.OW, (int)(cs.OH * cs.OW), (int)cs.K};
   return QVIT_OK;
 }
 

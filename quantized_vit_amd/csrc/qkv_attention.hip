@@ -492,14 +492,7 @@ static int qkv_attention_launch(const int8_t* A, int64_t B, int64_t N, int64_t K
     return QVIT_EINVAL;
   }
   if (B == 0) return QVIT_OK;
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
-  const int64_t grid = std::max<int64_t>(8, (int64_t)cus / 8 * 8);  // one workgroup per CU, a multiple of 8
+  const int64_t grid = std::max<int64_t>(8, (int64_t)qvit_device_cus() / 8 * 8);  // one workgroup per CU, a multiple of 8
   const int8_t* w = reinterpret_cast<const int8_t*>(Wp);
   const int8_t* tab = reinterpret_cast<const int8_t*>(epi_table);
 #define QVIT_QA_LAUNCH(OUTV, NKV, CLSV, TAB)                                                                     \

@@ -511,16 +511,10 @@ int qvit_im2col_quant_i8(const float* x, int64_t B, int64_t C, int64_t H, int64_
                          int8_t* codes, int64_t ldc, int64_t kpad, hipStream_t stream) {
   if (!x || !codes) return QVIT_ENULL;
   if (qvit_quant_status(qtype, d_quant, q_m, levels)) return QVIT_EINVAL;
-  if (B < 0 || C <= 0 || H <= 0 || W <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || ph < 0 ||
-      pw < 0 || dh <= 0 || dw <= 0)
-    return QVIT_EINVAL;
-  // the padded image has to hold the dilated kernel: checked on the extents, because the division below truncates
-  // toward zero and would turn an extent of -1 at a stride of 2 into one output
-  const int64_t eh = H + 2 * (int64_t)ph - (int64_t)dh * (kh - 1) - 1, ew = W + 2 * (int64_t)pw - (int64_t)dw * (kw - 1) - 1;
-  if (eh < 0 || ew < 0) return QVIT_EINVAL;
-  const int64_t OH = eh / sh + 1, OW = ew / sw + 1;
-  const int64_t K = C * kh * kw;
-  if (kpad < K || kpad % 16 || ldc < kpad) return QVIT_EINVAL;
+  ConvShape cs;
+  if (qvit_conv_shape(B, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw, cs)) return QVIT_EINVAL;
+  const int64_t OH = cs.OH, OW = cs.OW;
+  if (kpad < cs.K || kpad % 16 || ldc < kpad) return QVIT_EINVAL;
   if ((ldc % 16) || qvit_misaligned(15, codes)) return QVIT_EALIGN;
   if (B == 0) return QVIT_OK;
   const int64_t work = B * OH * OW * (kpad / 16);
@@ -551,13 +545,7 @@ int qvit_layernorm_quant_i8(const float* x, int64_t rows, int64_t cols, int64_t 
   const int nv = (int)((cols + 255) / 256);
   const dim3 grid((unsigned)((rows + 3) / 4));
   if (reg && nv <= 4) {  // persistent: as many workgroups as are co-resident, the table read once per workgroup
-    static const int cus = [] {
-      int dev = 0, n = 0;
-      if (hipGetDevice(&dev) != hipSuccess ||
-          hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-        n = 256;
-      return n;
-    }();
+    const int cus = qvit_device_cus();
     // workgroups per CU that are resident together (registers bound it: 5 at NV = 3); a grid past that
     // leaves a second, partly filled round of workgroups behind the first
     auto resident = [](const void* fn) {
@@ -601,13 +589,7 @@ int qvit_layernorm_quant_i8_t32(const float* x, int64_t rows, int64_t cols, int6
   if (rows < 0 || cols <= 0 || cols > 1024 || (cols & 3) || ldx < cols || kpad < cols || (kpad & 63)) return QVIT_EINVAL;
   if ((ldx & 3) || qvit_misaligned(15, x, gamma, beta, codes)) return QVIT_EALIGN;
   if (rows == 0) return QVIT_OK;
-  static const int cus = [] {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                                hipSuccess || n <= 0)
-      n = 256;
-    return n;
-  }();
+  const int cus = qvit_device_cus();
   auto resident = [](const void* fn) {
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, kThreads, 0) != hipSuccess || n <= 0) n = 4;

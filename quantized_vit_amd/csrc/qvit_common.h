@@ -308,3 +308,39 @@ static inline int qvit_backward_qtype_status(int qtype, bool& nonlinear) {
   nonlinear = q == QVIT_QT_NONLINEAR;
   return QVIT_OK;
 }
+
+// ---- host-side conv geometry and device query of the entry points --------------------------------------------
+// The output size of a convolution, once for every entry point that takes (B, C, H, W, kh .. dw): the shared sign
+// rules (B >= 0; C, H, W, k*, s*, d* >= 1; p* >= 0), then the padded image has to hold the dilated kernel. That is
+// checked on the extents eh, ew BEFORE the division, which truncates toward zero and would turn an extent of -1 at
+// a stride of 2 into one output. K = C kh kw is the patch length, M = B OH OW the patch count. Each entry point
+// keeps its own upper bounds; one that bounds its sizes does so before the call, so that nothing here overflows.
+struct ConvShape {
+  int64_t OH, OW, K, M;
+};
+static inline int qvit_conv_shape(int64_t B, int64_t C, int64_t H, int64_t W, int kh, int kw, int sh, int sw,
+                                  int64_t ph, int64_t pw, int dh, int dw, ConvShape& s) {
+  if (B < 0 || C < 1 || H < 1 || W < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 || dh < 1 ||
+      dw < 1)
+    return QVIT_EINVAL;
+  const int64_t eh = H + 2 * ph - (int64_t)dh * (kh - 1) - 1;   // (64-bit: the paddings arrive widened)
+  const int64_t ew = W + 2 * pw - (int64_t)dw * (kw - 1) - 1;
+  if (eh < 0 || ew < 0) return QVIT_EINVAL;
+  s.OH = eh / sh + 1;
+  s.OW = ew / sw + 1;
+  s.K = C * kh * kw;
+  s.M = B * s.OH * s.OW;
+  return QVIT_OK;
+}
+
+// CUs of the current device (256 when the query fails), asked once per process: the persistent grids are sized by it
+inline int qvit_device_cus() {
+  static const int cus = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) !=
+                                                hipSuccess || n <= 0)
+      n = 256;
+    return n;
+  }();
+  return cus;
+}

@@ -269,16 +269,13 @@ int64_t round64(int64_t v) { return (v + 63) / 64 * 64; }
 bool conv_wgrad_geo(int64_t B, int64_t C, int64_t H, int64_t W, int64_t N, int kh, int kw, int sh, int sw, int ph,
                     int pw, int dh, int dw, ConvGeo* geo) {
   const int64_t lim = 1 << 20;
-  if (B < 0 || C < 1 || H < 1 || W < 1 || N < 1 || kh < 1 || kw < 1 || sh < 1 || sw < 1 || ph < 0 || pw < 0 ||
-      dh < 1 || dw < 1)
-    return false;
+  // (the upper bounds first: they bound what qvit_conv_shape multiplies; a size below its range fails there)
   if (C > lim || H > lim || W > lim || N > lim || kh > 1024 || kw > 1024 || sh > lim || sw > lim || ph > lim ||
       pw > lim || dh > 1024 || dw > 1024)
     return false;
-  const int64_t eh = H + 2 * (int64_t)ph - (int64_t)dh * (kh - 1) - 1, ew = W + 2 * (int64_t)pw - (int64_t)dw * (kw - 1) - 1;
-  if (eh < 0 || ew < 0) return false;
-  const int64_t OH = eh / sh + 1, OW = ew / sw + 1;
-  const int64_t K = C * kh * kw, M = B * OH * OW;
+  ConvShape cs;
+  if (N < 1 || qvit_conv_shape(B, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw, cs)) return false;
+  const int64_t OH = cs.OH, OW = cs.OW, K = cs.K, M = cs.M;
   if (K > lim || OH * OW > (1 << 30) || M > (int64_t)INT32_MAX - 64) return false;
   if ((round64(N) / CW_TN) * (round64(K) / CW_TK) > (1 << 20)) return false;   // (grid and unit counts fit int32)
   *geo = ConvGeo{(int)B, (int)C, (int)H, (int)W, (int)N, kh, kw, sh, sw, ph, pw, dh, dw, (int)OH, (int)OW, (int)K, (int)M};

@@ -131,6 +131,42 @@ QVIT_DEV TileWalk tile_walk(int ntiles) {
   }
   return w;
 }
+
+// ---- shared by the two layer-0 kernels (ultra_conv0_mfma_kernel, ultra_conv0_int_mfma_kernel) ----------------
+// (Their lane and halo-quad mapping and the double-buffered loop itself are spelled out in each kernel: factored
+// out, the compiler orders the prologue differently and the kernels' code changes.)
+// tile t = (b tiles_y + ty) tiles_x + tx as (b, ty, tx); the walk advances t by a fixed team, so the
+// coordinates advance by the team's own with carries (no division per tile)
+struct C0Pos {
+  int b, ty, tx;
+};
+QVIT_DEV C0Pos c0_pos(int t, int tiles_y, int tiles_x) {
+  const int row = t / tiles_x;
+  return C0Pos{row / tiles_y, row - (row / tiles_y) * tiles_y, t - row * tiles_x};
+}
+QVIT_DEV C0Pos c0_advance(C0Pos p, const C0Pos& step, int tiles_y, int tiles_x) {
+  p.tx += step.tx;
+  if (p.tx >= tiles_x) p.tx -= tiles_x, p.ty += 1;
+  p.ty += step.ty;
+  if (p.ty >= tiles_y) p.ty -= tiles_y, p.b += 1;
+  p.b += step.b;
+  return p;
+}
+
+// the wave's pooled codes of a tile (2 rows x 16 columns x 16 channels) leave as 16-B pixels, 16 lanes per
+// 256-B output row; the wave reads back only what it wrote (its LDS operations complete in order). The loop issues
+// it after the next tile's halo loads: a store ahead of them would make their issue wait for its completion.
+QVIT_DEV void c0_flush(const int8_t* codes_w, int lane, int wave, int b, int ty0, int tx0, int Ho, int Wo,
+                       int8_t* __restrict__ out) {
+  __builtin_amdgcn_wave_barrier();
+  if (lane < 32) {
+    const int yo = ((ty0 + 4 * wave) >> 1) + (lane >> 4), xo = (tx0 >> 1) + (lane & 15);
+    const uint4 v = *reinterpret_cast<const uint4*>(codes_w + lane * C0_OUT);
+    if (yo < Ho && xo < Wo) *reinterpret_cast<uint4*>(out + (((int64_t)b * Ho + yo) * Wo + xo) * C0_OUT) = v;
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
 QVIT_DEV _Float16 hi_h(float x) { return (_Float16)x; }
 // codes of lanes 4k .. 4k + 3 (channels n .. n + 3) as one word in lane 4k (DPP quad permutes)
 QVIT_DEV uint32_t pack_quad(int code) {
@@ -191,19 +227,10 @@ __global__ __launch_bounds__(256, C0_OCC) void ultra_conv0_mfma_kernel(const flo
   const int tiles_y = (H + C0_TY - 1) / C0_TY, tiles_x = (W + C0_TX - 1) / C0_TX;
   const int ntiles = B * tiles_y * tiles_x;
   const int64_t HW = (int64_t)H * W;
-  // tile t = (b tiles_y + ty) tiles_x + tx as (b, ty, tx); the walk advances t by a fixed team, so the
-  // coordinates advance by the team's own with carries (no division per tile)
-  struct TPos {
-    int b, ty, tx;
-  };
-  auto tpos = [&](int t) __attribute__((always_inline)) {
-    const int row = t / tiles_x;
-    return TPos{row / tiles_y, row - (row / tiles_y) * tiles_y, t - row * tiles_x};
-  };
   // this thread's halo quad (hy, 4 qx .. 4 qx + 3) of tile t -> registers (zero outside the image)
   const int qy = tid / (C0_HX / 4), qx = tid - qy * (C0_HX / 4);
   c0f4 xin[3];
-  auto load_tile = [&](const TPos& p) __attribute__((always_inline)) {
+  auto load_tile = [&](const C0Pos& p) __attribute__((always_inline)) {
     if (tid >= C0_QUADS) return;
     const int b = p.b, ty0 = p.ty * C0_TY, tx0 = p.tx * C0_TX;
     const float* base = img + (int64_t)b * 3 * HW;
@@ -248,38 +275,18 @@ __global__ __launch_bounds__(256, C0_OCC) void ultra_conv0_mfma_kernel(const flo
   const TileWalk tw = tile_walk(ntiles);
   int t = tw.lo + tw.slot;
   if (t >= tw.hi) return;
-  TPos cur = tpos(t);
-  const TPos step = tpos(tw.team);
-  auto advance = [&](TPos p) __attribute__((always_inline)) {
-    p.tx += step.tx;
-    if (p.tx >= tiles_x) p.tx -= tiles_x, p.ty += 1;
-    p.ty += step.ty;
-    if (p.ty >= tiles_y) p.ty -= tiles_y, p.b += 1;
-    p.b += step.b;
-    return p;
-  };
+  C0Pos cur = c0_pos(t, tiles_y, tiles_x);
+  const C0Pos step = c0_pos(tw.team, tiles_y, tiles_x);
   load_tile(cur);
   stage_tile(smem[0]);
   __syncthreads();
-  // the wave's pooled codes of a tile (2 rows x 16 columns x 16 channels) leave as 16-B pixels, 16 lanes per
-  // 256-B output row; the wave reads back only what it wrote (its LDS operations complete in order). Issued
-  // after the next tile's halo loads: a store ahead of them would make their issue wait for its completion.
-  auto flush = [&](int b, int ty0, int tx0) __attribute__((always_inline)) {
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 32) {
-      const int yo = ((ty0 + 4 * wave) >> 1) + (lane >> 4), xo = (tx0 >> 1) + (lane & 15);
-      const uint4 v = *reinterpret_cast<const uint4*>(codes_l[wave] + lane * C0_OUT);
-      if (yo < Ho && xo < Wo) *reinterpret_cast<uint4*>(out + (((int64_t)b * Ho + yo) * Wo + xo) * C0_OUT) = v;
-    }
-    __builtin_amdgcn_wave_barrier();
-  };
   int pb = 0, pty = 0, ptx = 0;  // the previous tile, its codes still in codes_l
   for (int it = 0; t < tw.hi; t += tw.team, ++it) {
     const int8_t* buf = smem[it & 1];
     const int tn = t + tw.team;
-    const TPos nxt = advance(cur);
+    const C0Pos nxt = c0_advance(cur, step, tiles_y, tiles_x);
     if (tn < tw.hi) load_tile(nxt);  // lands while this tile computes
-    if (it > 0) flush(pb, pty, ptx);
+    if (it > 0) c0_flush(codes_l[wave], lane, wave, pb, pty, ptx, Ho, Wo, out);
     const int b = cur.b, ty0 = cur.ty * C0_TY, tx0 = cur.tx * C0_TX;
     pb = b, pty = ty0, ptx = tx0;
     cur = nxt;
@@ -330,7 +337,7 @@ __global__ __launch_bounds__(256, C0_OCC) void ultra_conv0_mfma_kernel(const flo
     if (tn < tw.hi) stage_tile(smem[(it + 1) & 1]);  // the other buffer: its last reader finished a barrier ago
     __syncthreads();
   }
-  flush(pb, pty, ptx);
+  c0_flush(codes_l[wave], lane, wave, pb, pty, ptx, Ho, Wo, out);
 }
 
 // ---- integer deploy (quantization.py:24-31,68-89; ultranet_param_gen.py) --------------------------------
@@ -386,17 +393,10 @@ __global__ __launch_bounds__(256, 4) void ultra_conv0_int_mfma_kernel(const uint
   const int tiles_y = (H + C0_TY - 1) / C0_TY, tiles_x = (W + C0_TX - 1) / C0_TX;
   const int ntiles = B * tiles_y * tiles_x;
   const int64_t HW = (int64_t)H * W;
-  struct TPos {
-    int b, ty, tx;
-  };
-  auto tpos = [&](int t) __attribute__((always_inline)) {
-    const int row = t / tiles_x;
-    return TPos{row / tiles_y, row - (row / tiles_y) * tiles_y, t - row * tiles_x};
-  };
   // this thread's halo quad (as the float kernel): per channel 4 bytes, staged as x - 128 in 4-channel pixels
   const int qy = tid / (C0_HX / 4), qx = tid - qy * (C0_HX / 4);
   uint32_t xin[3];
-  auto load_tile = [&](const TPos& p) __attribute__((always_inline)) {
+  auto load_tile = [&](const C0Pos& p) __attribute__((always_inline)) {
     if (tid >= C0_QUADS) return;
     const int b = p.b, ty0 = p.ty * C0_TY, tx0 = p.tx * C0_TX;
     const uint8_t* base = img + (int64_t)b * 3 * HW;
@@ -436,35 +436,18 @@ __global__ __launch_bounds__(256, 4) void ultra_conv0_int_mfma_kernel(const uint
   const TileWalk tw = tile_walk(ntiles);
   int t = tw.lo + tw.slot;
   if (t >= tw.hi) return;
-  TPos cur = tpos(t);
-  const TPos step = tpos(tw.team);
-  auto advance = [&](TPos p) __attribute__((always_inline)) {
-    p.tx += step.tx;
-    if (p.tx >= tiles_x) p.tx -= tiles_x, p.ty += 1;
-    p.ty += step.ty;
-    if (p.ty >= tiles_y) p.ty -= tiles_y, p.b += 1;
-    p.b += step.b;
-    return p;
-  };
+  C0Pos cur = c0_pos(t, tiles_y, tiles_x);
+  const C0Pos step = c0_pos(tw.team, tiles_y, tiles_x);
   load_tile(cur);
   stage_tile(smem[0]);
   __syncthreads();
-  auto flush = [&](int b, int ty0, int tx0) __attribute__((always_inline)) {  // as the float kernel
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 32) {
-      const int yo = ((ty0 + 4 * wave) >> 1) + (lane >> 4), xo = (tx0 >> 1) + (lane & 15);
-      const uint4 v = *reinterpret_cast<const uint4*>(codes_l[wave] + lane * C0_OUT);
-      if (yo < Ho && xo < Wo) *reinterpret_cast<uint4*>(out + (((int64_t)b * Ho + yo) * Wo + xo) * C0_OUT) = v;
-    }
-    __builtin_amdgcn_wave_barrier();
-  };
   int pb = 0, pty = 0, ptx = 0;
   for (int it = 0; t < tw.hi; t += tw.team, ++it) {
     const int8_t* buf = smem[it & 1];
     const int tn = t + tw.team;
-    const TPos nxt = advance(cur);
+    const C0Pos nxt = c0_advance(cur, step, tiles_y, tiles_x);
     if (tn < tw.hi) load_tile(nxt);
-    if (it > 0) flush(pb, pty, ptx);
+    if (it > 0) c0_flush(codes_l[wave], lane, wave, pb, pty, ptx, Ho, Wo, out);
     pb = cur.b, pty = cur.ty * C0_TY, ptx = cur.tx * C0_TX;
     cur = nxt;
     // A fragment: pixels px .. px + 3 of kernel row g (group 3 re-reads row 2: zero weights)
@@ -490,7 +473,7 @@ __global__ __launch_bounds__(256, 4) void ultra_conv0_int_mfma_kernel(const uint
     if (tn < tw.hi) stage_tile(smem[(it + 1) & 1]);
     __syncthreads();
   }
-  flush(pb, pty, ptx);
+  c0_flush(codes_l[wave], lane, wave, pb, pty, ptx, Ho, Wo, out);
 }
 
 // ---- layers 1..8: implicit GEMM conv on MFMA ------------------------------------------------------
@@ -1024,12 +1007,9 @@ __global__ void yolo_decode_kernel(const float* __restrict__ head, int B, int ny
 // persistent grid: every block resident at once (CUs x occupancy), at most one per tile
 template <class K>
 int64_t resident_grid(K kernel, int64_t ntiles) {
-  int dev = 0, cus = 0, occ = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) !=
-                                              hipSuccess || cus <= 0)
-    cus = 256;
+  int occ = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, 0) != hipSuccess || occ <= 0) occ = 1;
-  return std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)cus * occ));
+  return std::max<int64_t>(1, std::min<int64_t>(ntiles, (int64_t)qvit_device_cus() * occ));
 }
 
 int grid_cap(int64_t work, int per = 256) {

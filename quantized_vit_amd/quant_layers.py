@@ -1142,8 +1142,7 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
         sh, sw = self.stride
         ph, pw = self.padding
         dh, dw = self.dilation
-        OH = (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1
-        OW = (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+        OH, OW = _lib.conv_out_hw(H, W, self.kernel_size, self.stride, self.padding, self.dilation)
         codes = torch.empty((B * OH * OW, plan.kpad), dtype=torch.int8, device=x.device)
         _lib.im2col_quant_i8(x, kh, kw, sh, sw, ph, pw, dh, dw, plan.qtype, plan.d_act, plan.qm_act, plan.t_act, 0,
                              codes, plan.kpad)

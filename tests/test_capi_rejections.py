@@ -82,12 +82,26 @@ PACK_WEIGHT = [
 ]
 
 
+def _ax(one, both):
+    return both if one is None else one
+
+
+# Geometries that every entry point with (kh .. dw) arguments rejects with QVIT_EINVAL, as overrides of a valid call
+# with a 3 x 3 kernel, stride 1, padding 1 on an image of at least 5 x 5: the extent H + 2 ph - dh (kh - 1) - 1 of one
+# axis is -1 at a stride of 2 (a division that truncates toward zero would make one output of it), or one argument of
+# one axis is out of range while the other axis is valid.
+CONV_GEO_BAD = [
+    dict(W=2, pw=0, sw=2), dict(H=2, ph=0, sh=2),                    # a kernel one past the image, stride 2
+    dict(W=4, pw=0, sw=2, dw=2), dict(H=4, ph=0, sh=2, dh=2),        # the image holds the kernel, not the dilated one
+    dict(kh=0), dict(kw=0), dict(sh=0), dict(sw=0), dict(dh=0), dict(dw=0), dict(ph=-1), dict(pw=-1),
+]
+
+
 def im2col(lib, x=A0, B=1, C=3, H=8, W=8, k=3, s=1, p=1, dil=1, qtype=LIN, d=A1, qm=A2, t=None, levels=0, codes=A3,
            ldc=32, kpad=32, kh=None, kw=None, sh=None, sw=None, ph=None, pw=None, dh=None, dw=None):
     """k, s, p, dil go to both axes; kh .. dw override one axis each."""
-    ax = lambda one, both: both if one is None else one
-    return lib.qvit_im2col_quant_i8(_p(x), B, C, H, W, ax(kh, k), ax(kw, k), ax(sh, s), ax(sw, s), ax(ph, p), ax(pw, p),
-                                    ax(dh, dil), ax(dw, dil), qtype, _p(d), _p(qm), _p(t), levels, _p(codes), ldc, kpad,
+    return lib.qvit_im2col_quant_i8(_p(x), B, C, H, W, _ax(kh, k), _ax(kw, k), _ax(sh, s), _ax(sw, s), _ax(ph, p),
+                                    _ax(pw, p), _ax(dh, dil), _ax(dw, dil), qtype, _p(d), _p(qm), _p(t), levels, _p(codes), ldc, kpad,
                                     None)
 
 
@@ -221,10 +235,19 @@ ACT_BACKWARD = [
 ]
 
 
-def conv_wgrad(lib, G=A0, X=A1, B=2, C=3, H=5, W=7, N=5, k=3, s=1, p=1, levels=15, dW=A2, ws=A3, wsb=None):
+def conv_wgrad_geo(B=2, C=3, H=5, W=7, N=5, k=3, s=1, p=1, dil=1, kh=None, kw=None, sh=None, sw=None, ph=None, pw=None,
+                   dh=None, dw=None):
+    """The geometry arguments of qvit_conv_wgrad and its workspace query: k, s, p, dil go to both axes; kh .. dw
+    override one axis each."""
+    return (B, C, H, W, N, _ax(kh, k), _ax(kw, k), _ax(sh, s), _ax(sw, s), _ax(ph, p), _ax(pw, p), _ax(dh, dil),
+            _ax(dw, dil))
+
+
+def conv_wgrad(lib, G=A0, X=A1, levels=15, dW=A2, ws=A3, wsb=None, **geo):
+    geo = conv_wgrad_geo(**geo)
     if wsb is None:
-        wsb = max(0, int(lib.qvit_conv_wgrad_workspace_bytes(B, C, H, W, N, k, k, s, s, p, p, 1, 1)))
-    return lib.qvit_conv_wgrad(_p(G), _p(X), B, C, H, W, N, k, k, s, s, p, p, 1, 1, levels, _p(dW), _p(ws), wsb, None)
+        wsb = max(0, int(lib.qvit_conv_wgrad_workspace_bytes(*geo)))
+    return lib.qvit_conv_wgrad(_p(G), _p(X), *geo, levels, _p(dW), _p(ws), wsb, None)
 
 
 CONV_WGRAD = [
@@ -232,6 +255,9 @@ CONV_WGRAD = [
     (dict(levels=128), EINVAL), (dict(G=A0 + 2), EALIGN), (dict(X=A1 + 1), EALIGN), (dict(dW=A2 + 2), EALIGN),
     (dict(ws=A3 + 8), EALIGN), (dict(levels=0, G=A0 + 2), EINVAL), (dict(s=0, wsb=1 << 20, ws=A3 + 8), EINVAL),
     (dict(wsb=64), EINVAL), (dict(wsb=64, ws=A3 + 8), EALIGN),   # here the workspace size is looked at last
+    *[(geo, EINVAL) for geo in CONV_GEO_BAD],
+    # a bad extent is looked at after the null pointers and before the alignment
+    (dict(W=2, pw=0, sw=2, G=A0 + 2), EINVAL), (dict(W=2, pw=0, sw=2, G=None), ENULL),
 ]
 
 
@@ -425,9 +451,12 @@ GEMM_WONLY = [
 ]
 
 
-def conv_wonly(lib, fused=False, X=A0, B=1, C=3, H=8, W=8, k=3, s=1, p=1, Wp=A1, wfmt=_lib.W4, N=16, npad=256, K=128,
-               d_wt=A2, bias=None, bn_a=A4, bn_s=A5, levels=15, Y=A3):
-    head = (_p(X), B, C, H, W, k, k, s, s, p, p, 1, 1, _p(Wp), wfmt, N, npad, K, _p(d_wt), _p(bias))
+def conv_wonly(lib, fused=False, X=A0, B=1, C=3, H=8, W=8, k=3, s=1, p=1, dil=1, Wp=A1, wfmt=_lib.W4, N=16, npad=256,
+               K=128, d_wt=A2, bias=None, bn_a=A4, bn_s=A5, levels=15, Y=A3, kh=None, kw=None, sh=None, sw=None, ph=None,
+               pw=None, dh=None, dw=None):
+    """k, s, p, dil go to both axes; kh .. dw override one axis each."""
+    head = (_p(X), B, C, H, W, _ax(kh, k), _ax(kw, k), _ax(sh, s), _ax(sw, s), _ax(ph, p), _ax(pw, p), _ax(dh, dil),
+            _ax(dw, dil), _p(Wp), wfmt, N, npad, K, _p(d_wt), _p(bias))
     if fused:
         return lib.qvit_conv_wonly_bn_act(*head, _p(bn_a), _p(bn_s), levels, _p(Y), None)
     return lib.qvit_conv_wonly(*head, _p(Y), None, 0, None)
@@ -441,6 +470,9 @@ CONV_WONLY = [
     (dict(Y=None), ENULL), (dict(X=None, s=0), ENULL), (dict(wfmt=5), EINVAL), (dict(s=0), EINVAL), (dict(K=100), EINVAL),
     (dict(H=1, W=1, p=0), EINVAL), (dict(s=0, Wp=A1 + 8), EINVAL), (dict(K=100, bias=A6 + 8), EINVAL), (dict(B=0), OK),
     (dict(B=0, Wp=A1 + 8), EALIGN),
+    *[(geo, EINVAL) for geo in CONV_GEO_BAD],
+    # a bad extent is looked at after the null pointers and before the alignment
+    (dict(W=2, pw=0, sw=2, Wp=A1 + 8), EINVAL), (dict(W=2, pw=0, sw=2, Y=None), ENULL),
 ]
 CONV_WONLY_BN_ACT = CONV_WONLY + [
     (dict(bn_a=None), ENULL), (dict(bn_s=None, levels=0), ENULL), (dict(bn_a=None, Wp=A1 + 8), EALIGN),
@@ -642,6 +674,12 @@ def test_rejection_table(lib, call, rows):
 def test_every_aligned_pointer_is_checked(lib, call):
     for arg, (addr, align) in ALIGNED[call].items():   # (only the misaligned call is made: the aligned one would launch)
         assert call(lib, **{arg: addr + align // 2}) == EALIGN, (call.__name__, arg, align)
+
+
+def test_conv_wgrad_workspace_query_rejects_the_same_geometries(lib):
+    assert int(lib.qvit_conv_wgrad_workspace_bytes(*conv_wgrad_geo())) > 0
+    for geo in CONV_GEO_BAD:
+        assert int(lib.qvit_conv_wgrad_workspace_bytes(*conv_wgrad_geo(**geo))) < 0, geo
 
 
 def test_every_row_is_answered_before_a_launch():

@@ -104,3 +104,11 @@ def test_padding_cases_have_rows_outside_the_image():
         else:
             assert float(per_row[:, 0].sum()) == 0 and float(per_row[:, oh - 1].sum()) == 0
             assert float(per_row.sum()) > 0
+
+
+def test_lib_conv_out_hw_matches_the_table():
+    """The one output-size formula of the Python wrappers against the table's own (no library is loaded)."""
+    from quantized_vit_amd import _lib
+    assert len(G.CASES) == 16
+    for case in G.CASES:
+        assert _lib.conv_out_hw(case.H, case.W, case.k, case.s, case.p, case.d) == case.out_hw, case.id

@@ -1,6 +1,6 @@
 // Experiment (round 4, not built into the library): the ping-pong schedule for the int8-code GEMM epilogues
 // (fc1), as it ran inside quantized_vit_amd/csrc/gemm_w4a8.hip (it uses that file's Geo, Frags, EpiArgs, epilogue
-// helpers and launcher; to rebuild it, paste it back above device_cus() and route the I8 / I8_GELU launches of
+// helpers and launcher; to rebuild it, paste it back above launch() and route the I8 / I8_GELU launches of
 // launch() to it). Bit-identical to gemm_kernel (tests/test_gpu_gemm_pp.py at the time), and slower: fc1
 // 182-219 us in the model vs 124-131 us, 205-234 us vs 145-169 us in tools/gemm_bench.py
 // (profiles/r04_gemm_pingpong_ab.txt).
