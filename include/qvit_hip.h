@@ -699,8 +699,27 @@ int qvit_gemm_qkv_split(const int8_t* A, int64_t M, int64_t K, int64_t lda,
                         int64_t seq, float in_scale, void* qkv_hi, void* qkv_lo, hipStream_t stream);
 
 /*
- * qvit_attention on the split operands of qvit_gemm_qkv_split (planes [B][3H][N][64], in_scale the
- * same power of two): identical arithmetic; K/V blocks stream into LDS by DMA with no conversion.
+ * qvit_gemm_qkv_split with the head width as an argument: planes fp16 [B][N / head_dim][seq][head_dim], plane
+ * p = n / head_dim, element (b, p, t, n % head_dim); the same value arithmetic (x as QVIT_EPI_F32, hi = f16(x s),
+ * lo = f16(x s - hi)). head_dim is 64 or 80 and N % head_dim == 0. At 64 the bytes are those of qvit_gemm_qkv_split;
+ * at 80 a plane row is 160 B, so rows stay 16-B aligned.
+ * Order of the checks (part of the ABI), the same list for both entry points, qvit_gemm_qkv_split with head_dim 64:
+ * NULL pointers (QVIT_ENULL); wfmt; head_dim not 64 or 80; the sizes, N % head_dim among them; the seq / in_scale
+ * rules; K of the 4-bit formats (all QVIT_EINVAL); then alignment (QVIT_EALIGN): lda and A / Wp, the planes, bias; then
+ * M == 0 is QVIT_OK. So a bad head_dim wins over every seq and alignment rule and loses to NULL and wfmt.
+ */
+int qvit_gemm_qkv_split_hd(const int8_t* A, int64_t M, int64_t K, int64_t lda,
+                           const void* Wp, int wfmt, int64_t N, int64_t npad,
+                           const float* d_act, const float* d_wt, const float* bias,
+                           int64_t seq, int64_t head_dim, float in_scale, void* qkv_hi, void* qkv_lo,
+                           hipStream_t stream);
+
+/*
+ * qvit_attention on the split operands of qvit_gemm_qkv_split / qvit_gemm_qkv_split_hd (planes
+ * [B][3H][N][head_dim], head_dim 64 or 80, in_scale the same power of two): identical arithmetic, bit for bit;
+ * K/V blocks stream into LDS by DMA with no conversion. Both out modes at both widths (unlike qvit_attention, whose
+ * int8 epilogue is for 64 only); ldo >= H * head_dim. Any other head_dim is QVIT_EINVAL, at the position the
+ * head_dim != 64 check always had (after NULL and the table's alignment, before the sizes).
  * epi_table (QVIT_ATT_I8 only, nullable): a qvit_epi_table_build table with QVIT_EPI_I8 semantics for
  * the output quantizer (<= 2046 buckets; used only if valid, results never depend on it).
  */

@@ -115,6 +115,8 @@ _SIGNATURES = {
                        _i32, _c_p],
     "qvit_gemm_qkv_split": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i64, _f32, _c_p,
                             _c_p, _c_p],
+    "qvit_gemm_qkv_split_hd": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i64, _i64, _f32, _c_p,
+                               _c_p, _c_p],
     "qvit_qkv_attention": [_c_p, _i64, _i64, _i64, _i64, _c_p, _i32, _i64, _c_p, _c_p, _c_p, _i64, _i64, _f32, _f32,
                            _i32, _c_p, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
     "qvit_qkv_attention_q": [_c_p, _i64, _i64, _i64, _i64, _i64, _c_p, _i32, _i64, _c_p, _c_p, _c_p, _i64, _i64, _f32,
@@ -740,11 +742,17 @@ def attention_backward(qkv: torch.Tensor, out: torch.Tensor, grad_out: torch.Ten
 
 def gemm_qkv_split(A: torch.Tensor, M: int, K: int, packed: torch.Tensor, wfmt: int, N: int, npad: int,
                    d_act: torch.Tensor, d_wt: torch.Tensor, bias_pad: Optional[torch.Tensor], seq: int,
-                   in_scale: float, hi: torch.Tensor, lo: torch.Tensor):
-    """qkv projection as fp16 hi/lo planes [B][N/64][seq][64] of in_scale * x (qvit_gemm_qkv_split)."""
+                   in_scale: float, hi: torch.Tensor, lo: torch.Tensor, head_dim: int = 64):
+    """qkv projection as fp16 hi/lo planes [B][N/head_dim][seq][head_dim] of in_scale * x (qvit_gemm_qkv_split;
+    qvit_gemm_qkv_split_hd for a head_dim other than 64)."""
     _require_gpu(A, "codes")
     assert hi.dtype == torch.float16 and lo.dtype == torch.float16 and hi.is_contiguous() and lo.is_contiguous()
     assert hi.numel() >= M * N and lo.numel() >= M * N
+    if head_dim != 64:
+        _check(load().qvit_gemm_qkv_split_hd(_ptr(A), M, K, A.stride(0), _ptr(packed), wfmt, N, npad, _ptr(d_act),
+                                             _ptr(d_wt), _ptr(bias_pad), seq, head_dim, in_scale, _ptr(hi), _ptr(lo),
+                                             _stream(A.device)), "qvit_gemm_qkv_split_hd")
+        return hi, lo
     _check(load().qvit_gemm_qkv_split(_ptr(A), M, K, A.stride(0), _ptr(packed), wfmt, N, npad, _ptr(d_act),
                                       _ptr(d_wt), _ptr(bias_pad), seq, in_scale, _ptr(hi), _ptr(lo),
                                       _stream(A.device)), "qvit_gemm_qkv_split")

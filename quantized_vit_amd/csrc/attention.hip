@@ -22,8 +22,8 @@
 // LDS images (128-B rows of 64 fp16), XOR-swizzled, conflict-free for every read and write:
 //   K: 16-B chunk c of row r at c ^ ((r >> 1) & 7)        (ds_read_b128 A fragments)
 //   V: 32-B block b of row r at b ^ ((r >> 1) & 3)        (ds_read_b64_tr_b16 transposed reads)
-// attn_kernel also has a head dim 80 instantiation (fp32 output; ViT-Huge/14): 64 + 16 columns, the 16 in tail
-// images and a K = 16 MFMA step (attn_common.h), 3 query tiles per wave.
+// attn_kernel (fp32 output) and attn_split_kernel (both outputs) also have head dim 80 instantiations (ViT-Huge/14):
+// 64 + 16 columns, the 16 in tail images and a K = 16 MFMA step (attn_common.h), 3 query tiles per wave.
 #include "attn_common.h"
 
 #include <algorithm>
@@ -195,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void attn_kernel(const float* __restrict__ 
                             EpiLds{nullptr, 0.f, 0.f, 0.f}, st16);
 }
 
-// head dim 80, fp32 output only: 3 query tiles per wave (192 queries per workgroup); 4 do not fit in 256
+// head dim 80 of attn_kernel (fp32 output only): 3 query tiles per wave (192 queries per workgroup); 4 do not fit in 256
 // registers
 constexpr int QTW80 = 3;
 constexpr int QG80 = NWAVES * QTW80 * 16;
@@ -223,14 +223,46 @@ QVIT_DEV void block_sync() {
 constexpr int QB = 64;  // queries per query block
 constexpr int TBL_BYTES = 16384;  // int8 epilogue code table (<= 2046 buckets): 2 x (64 + 16) KiB per CU
 
-template <int OUT>
-__global__ __launch_bounds__(256, 2) void attn_split_kernel(const _Float16* __restrict__ hi,
+// Head dim 80 (planes [B][3H][N][80], 160-B rows): a ring stage is the four images plus four 1-KiB tails
+// (stage_bytes<80>, 20 KiB), for key blocks (K hi, K lo, V hi, V lo tails of 32 rows, as attend<QT, 80> reads them)
+// and for query blocks (hi tail of 64 rows, then lo tail: 2 KiB each). The images take columns 0 .. 63 of a row as
+// at 64; a tail takes columns 64 .. 79 (32 B: two lanes per row) to byte 32 r, unswizzled, so a 1-KiB tail piece is
+// one wave-DMA with consecutive lanes writing consecutive 16 B. Wave w issues tail piece w of either block kind:
+// five DMAs per wave per block of both kinds, which is what the counted waits below rely on.
+// QT query tiles per wave (the workgroup owns NWAVES * QT * 16 queries = QT query blocks); RING stages, RING - 1
+// blocks in flight. (diagnostic builds: -DQVIT_SPLIT80_QT / -DQVIT_SPLIT80_RING for the A/B of DESIGN.md section 20)
+#ifndef QVIT_SPLIT80_QT
+#define QVIT_SPLIT80_QT 3
+#endif
+#ifndef QVIT_SPLIT80_RING
+#define QVIT_SPLIT80_RING 3
+#endif
+constexpr int SQT80 = QVIT_SPLIT80_QT;
+constexpr int SRING80 = QVIT_SPLIT80_RING;
+
+// ring slot of stream block p (RING is 4 or 3)
+#define QVIT_RING_SLOT(p) (RING == 4 ? ((p) & 3) : (int)((unsigned)(p) % 3u))
+
+// workgroups per CU the registers allow: 4 tiles per wave at head dim 80 need more than 256 (section 20)
+template <int D, int QT>
+constexpr int split_wgs = (D == HD80 && QT > 3) ? 1 : 2;
+
+template <int OUT, int D, int RING>
+constexpr int split_lds_bytes = RING * stage_bytes<D> + (OUT == 1 ? TBL_BYTES : 0);
+
+template <int OUT, int D = HD, int QT = QTW, int RING = SRING>
+__global__ __launch_bounds__(256, (split_wgs<D, QT>)) void attn_split_kernel(const _Float16* __restrict__ hi,
                                                             const _Float16* __restrict__ lo, int N, int H, int nunits,
                                                             float scale, float in_scale, void* __restrict__ out,
                                                             int64_t ldo, int out_qtype, const float* out_d,
                                                             const float* out_qm, const float* out_t, int out_levels,
                                                             const int8_t* __restrict__ epi_table) {
-  __shared__ __attribute__((aligned(16))) int8_t smem[SRING * STAGE + (OUT == 1 ? TBL_BYTES : 0)];
+  static_assert(RING == 3 || RING == 4, "the counted waits below are written for 2 or 3 blocks in flight");
+  constexpr int STAGE = stage_bytes<D>;
+  constexpr int QG = NWAVES * QT * 16;      // queries per workgroup
+  constexpr int LEAD = RING - 1;            // blocks issued ahead of the one being waited for
+  constexpr int DPB = D == HD80 ? 5 : 4;    // DMAs per wave per stream block, query and key blocks alike
+  __shared__ __attribute__((aligned(16))) int8_t smem[split_lds_bytes<OUT, D, RING>];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -244,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(const _Float16* __re
     if (epi_table != nullptr) {  // the code table -> LDS, once per workgroup
       const EpiTableHdr hd = *reinterpret_cast<const EpiTableHdr*>(epi_table);
       if (hd.valid != 0 && hd.nb >= 1 && 16 + 8 * hd.nb <= TBL_BYTES) {
-        int8_t* tl = smem + SRING * STAGE;
+        int8_t* tl = smem + RING * STAGE;
         for (int k = tid; k < (16 + 8 * hd.nb + 15) / 16; k += 256)
           reinterpret_cast<uint4*>(tl)[k] = reinterpret_cast<const uint4*>(epi_table)[k];
         tb = EpiLds{tl + sizeof(EpiTableHdr), hd.c0, hd.inv_w, epi_top(hd.nb)};
@@ -272,17 +304,17 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(const _Float16* __re
   }
   const int my_units = (uhi - ulo - slot + team - 1) / team;  // unit j: ulo + slot + j * team
   const int total = my_units * per;
-  const int64_t plane = (int64_t)N * HD;
+  const int64_t plane = (int64_t)N * D;
 
   const uint32_t lds0 = lds_addr(smem);
-  // DMA of stream block p into ring slot p % SRING
+  // DMA of stream block p into ring slot p % RING
   auto issue = [&](int p) {
     const int j = p / per, idx = p - j * per;
     const int unit = ulo + slot + j * team;
     const int grp = unit % ngroups, bh = unit / ngroups;
     const int h = bh % H, b = bh / H;
     const int64_t qoff = ((int64_t)b * 3 * H + h) * plane;
-    const uint32_t base = __builtin_amdgcn_readfirstlane(lds0 + (p & (SRING - 1)) * STAGE);
+    const uint32_t base = __builtin_amdgcn_readfirstlane(lds0 + QVIT_RING_SLOT(p) * STAGE);
     if (idx < nqb) {  // query block: rows 16w .. 16w+15 of the hi and lo images (K layout)
 #pragma unroll
       for (int pc = 0; pc < 2; ++pc) {
@@ -290,10 +322,16 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(const _Float16* __re
         int q = grp * QG + idx * QB + r;
         q = q < N ? q : N - 1;
         const int kc = ((lane & 7) ^ ((r >> 1) & 7)) << 4;
-        const int64_t e = qoff + (int64_t)q * HD;
+        const int64_t e = qoff + (int64_t)q * D;
         const uint32_t d = base + (16 * wave + 8 * pc) * 128;
         dma16(reinterpret_cast<const int8_t*>(hi + e) + kc, __builtin_amdgcn_readfirstlane(d));
         dma16(reinterpret_cast<const int8_t*>(lo + e) + kc, __builtin_amdgcn_readfirstlane(d + QB * 128));
+      }
+      if constexpr (D == HD80) {  // tail piece w: rows 32 (w & 1) .. + 31 of the hi (w < 2) or lo tail
+        int q = grp * QG + idx * QB + 32 * (wave & 1) + (lane >> 1);
+        q = q < N ? q : N - 1;
+        const _Float16* src = (wave & 2 ? lo : hi) + qoff + (int64_t)q * D + HD + 8 * (lane & 1);
+        dma16(src, __builtin_amdgcn_readfirstlane(base + 4 * IMG + wave * TAIL));
       }
     } else {          // key block: rows 8w .. 8w+7 of K hi, K lo, V hi, V lo
       const int kb = idx - nqb;
@@ -303,23 +341,31 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(const _Float16* __re
       key = key < N ? key : N - 1;  // keys past N: a valid row, masked out of the softmax
       const int kc = (sc ^ ((r >> 1) & 7)) << 4;
       const int vb = (((sc >> 1) ^ ((r >> 1) & 3)) << 5) | ((sc & 1) << 4);
-      const int64_t ke = qoff + H * plane + (int64_t)key * HD;
+      const int64_t ke = qoff + H * plane + (int64_t)key * D;
       const int64_t ve = ke + H * plane;
       const uint32_t d = base + wave * 1024;
       dma16(reinterpret_cast<const int8_t*>(hi + ke) + kc, __builtin_amdgcn_readfirstlane(d));
       dma16(reinterpret_cast<const int8_t*>(lo + ke) + kc, __builtin_amdgcn_readfirstlane(d + IMG));
       dma16(reinterpret_cast<const int8_t*>(hi + ve) + vb, __builtin_amdgcn_readfirstlane(d + 2 * IMG));
       dma16(reinterpret_cast<const int8_t*>(lo + ve) + vb, __builtin_amdgcn_readfirstlane(d + 3 * IMG));
+      if constexpr (D == HD80) {  // tail w (K hi, K lo, V hi, V lo): all 32 rows, the same clamp as above
+        int tkey = kb * KB + (lane >> 1);
+        tkey = tkey < N ? tkey : N - 1;
+        const _Float16* src = (wave & 1 ? lo : hi) + qoff + (wave & 2 ? 2 : 1) * H * plane + (int64_t)tkey * D + HD +
+                              8 * (lane & 1);
+        dma16(src, __builtin_amdgcn_readfirstlane(base + 4 * IMG + wave * TAIL));
+      }
     }
   };
-  // block p landed for every wave (4 DMAs per wave per block; up to two younger blocks in flight) and
-  // every wave is done with block p - 1, whose slot block p + 3 takes
+  // block p landed for every wave (DPB DMAs per wave per block, 4 at head dim 64 and 5 at 80, whichever kind the
+  // blocks are; up to LEAD - 1 younger blocks in flight) and every wave is done with block p - 1, whose slot
+  // block p + LEAD takes
   auto sync = [&](int p) {
     const int ahead = total - 1 - p;
-    if (ahead >= 2) block_sync<8>();
-    else if (ahead == 1) block_sync<4>();
+    if (ahead >= LEAD - 1) block_sync<(LEAD - 1) * DPB>();
+    else if (LEAD > 2 && ahead == 1) block_sync<DPB>();
     else block_sync<0>();
-    if (p + 3 < total) issue(p + 3);
+    if (p + LEAD < total) issue(p + LEAD);
   };
 
   int koffs[2][2], voffs[4];
@@ -327,55 +373,65 @@ __global__ __launch_bounds__(256, 2) void attn_split_kernel(const _Float16* __re
   const float sl2 = scale * LOG2E / (in_scale * in_scale);
 
   Stamps sp;
-  for (int p = 0; p < 3 && p < total; ++p) issue(p);
+  for (int p = 0; p < LEAD && p < total; ++p) issue(p);
   int p = 0;
   for (int j = 0; j < my_units; ++j) {
     const int unit = ulo + slot + j * team;
     const int grp = unit % ngroups, bh = unit / ngroups;
     const int h = bh % H, b = bh / H;
     const int q0 = grp * QG;
-    const int wr = (wave + unit) & (NWAVES - 1);  // the wave owning a 4th tile rotates by unit
-    h8 qh[QTW][2], ql[QTW][2];
+    const int wr = (wave + unit) & (NWAVES - 1);  // the wave owning a query block's last tile rotates by unit
+    h8 qh[QT][2], ql[QT][2];
+    [[maybe_unused]] TailFrag<QT, D> qt;
     int nt = 0;
 #pragma unroll
-    for (int i = 0; i < QTW; ++i) {
+    for (int i = 0; i < QT; ++i) {
       if (i < nqb) {
         sp.mark(4);
         sync(p);
         sp.mark(0);
-        const int8_t* st = smem + (p & (SRING - 1)) * STAGE;
+        const int8_t* st = smem + QVIT_RING_SLOT(p) * STAGE;
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
           const int off = koff(16 * wr + fr, g + 4 * c);
           qh[i][c] = lds_h8(st, off);
           ql[i][c] = lds_h8(st + QB * 128, off);
         }
+        if constexpr (D == HD80) {  // columns 64 + 4 g .. + 3 of the tile's row fr, from the hi and lo tails
+          qt.h[i] = lds_h4(st + 4 * IMG, ktoff(16 * wr + fr, g));
+          qt.l[i] = lds_h4(st + 4 * IMG + 2 * TAIL, ktoff(16 * wr + fr, g));
+        }
         ++p;
       } else {  // no such query block: zeros (the tile is skipped or discarded)
         qh[i][0] = qh[i][1] = ql[i][0] = ql[i][1] = h8{};
+        if constexpr (D == HD80) qt.h[i] = qt.l[i] = h4{};
       }
       nt += (i < nqb && q0 + 16 * (wr + NWAVES * i) < N) ? 1 : 0;
     }
-    float m[QTW], l[QTW];
-    f4 o[QTW][4];
+    float m[QT], l[QT];
+    f4 o[QT][D / 16];
 #pragma unroll
-    for (int i = 0; i < QTW; ++i) {
+    for (int i = 0; i < QT; ++i) {
       m[i] = -INFINITY;
       l[i] = 0.f;
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) o[i][dt] = f4{0.f, 0.f, 0.f, 0.f};
+      for (int dt = 0; dt < D / 16; ++dt) o[i][dt] = f4{0.f, 0.f, 0.f, 0.f};
     }
     sp.mark(5);
     for (int kb = 0; kb < nkb; ++kb, ++p) {
       sync(p);
       sp.mark(0);
-      attend_n(nt, (kb + 1) * KB > N, smem + (p & (SRING - 1)) * STAGE, qh, ql, m, l, o, koffs, voffs,
-               kb * KB + 4 * g, N, sl2, sp);
+      if constexpr (D == HD)
+        attend_n(nt, (kb + 1) * KB > N, smem + QVIT_RING_SLOT(p) * STAGE, qh, ql, m, l, o, koffs, voffs,
+                 kb * KB + 4 * g, N, sl2, sp);
+      else
+        attend<QT, IMG, false, D>(nt, (kb + 1) * KB > N, smem + QVIT_RING_SLOT(p) * STAGE, qh, ql, m, l, o, koffs,
+                                   voffs, kb * KB + 4 * g, N, sl2, sp, qt);
     }
-    bool tv[QTW];
+    bool tv[QT];
 #pragma unroll
-    for (int i = 0; i < QTW; ++i) tv[i] = i < nt;
-    attend_store<OUT, QTW>(tv, l, o, wr, NWAVES, q0, N, b, h, in_scale, out, ldo, qp, tb, st16);
+    for (int i = 0; i < QT; ++i) tv[i] = i < nt;
+    attend_store<OUT, QT, D>(tv, l, o, wr, NWAVES, q0, N, b, h, in_scale, out, ldo, qp, tb, st16);
   }
   sp.mark(4);
   sp.flush();
@@ -425,8 +481,8 @@ extern "C" int qvit_attention_split(const void* qkv_hi, const void* qkv_lo, int6
                                     hipStream_t stream) {
   if (!qkv_hi || !qkv_lo || !out) return QVIT_ENULL;
   if (qvit_misaligned(15, epi_table)) return QVIT_EALIGN;
-  if (head_dim != HD) return QVIT_EINVAL;
-  if (B < 0 || N <= 0 || H <= 0 || ldo < H * HD) return QVIT_EINVAL;
+  if (head_dim != HD && head_dim != HD80) return QVIT_EINVAL;
+  if (B < 0 || N <= 0 || H <= 0 || ldo < H * head_dim) return QVIT_EINVAL;
   if (B * N > INT32_MAX || N > (1 << 20) || !(in_scale > 0.f)) return QVIT_EINVAL;
   if (qvit_misaligned(15, qkv_hi, qkv_lo)) return QVIT_EALIGN;
   if (out_mode == QVIT_ATT_F32) {
@@ -438,11 +494,26 @@ extern "C" int qvit_attention_split(const void* qkv_hi, const void* qkv_lo, int6
     return QVIT_EINVAL;
   }
   if (B == 0) return QVIT_OK;
-  const int64_t ngroups = (N + QG - 1) / QG;
+  const int64_t qg = head_dim == HD80 ? NWAVES * SQT80 * 16 : QG;
+  const int64_t ngroups = (N + qg - 1) / qg;
   const int64_t nblk = B * H * ngroups;
   if (nblk > INT32_MAX) return QVIT_EINVAL;
   const _Float16* hi = reinterpret_cast<const _Float16*>(qkv_hi);
   const _Float16* lo = reinterpret_cast<const _Float16*>(qkv_lo);
+  if (head_dim == HD80) {
+    // resident workgroups per CU: what the ring (and the table) leave of 160 KiB of LDS, two at the most
+    const int lds = out_mode == QVIT_ATT_F32 ? split_lds_bytes<0, HD80, SRING80> : split_lds_bytes<1, HD80, SRING80>;
+    const int64_t grid80 = std::min<int64_t>(nblk, std::min(split_wgs<HD80, SQT80>, 160 * 1024 / lds) * (int64_t)qvit_device_cus());
+    if (out_mode == QVIT_ATT_F32)
+      hipLaunchKernelGGL((attn_split_kernel<0, HD80, SQT80, SRING80>), dim3((unsigned)grid80), dim3(256), 0, stream, hi,
+                         lo, (int)N, (int)H, (int)nblk, scale, in_scale, out, ldo, out_qtype, out_d, out_qm, out_t,
+                         out_levels, nullptr);
+    else
+      hipLaunchKernelGGL((attn_split_kernel<1, HD80, SQT80, SRING80>), dim3((unsigned)grid80), dim3(256), 0, stream, hi,
+                         lo, (int)N, (int)H, (int)nblk, scale, in_scale, out, ldo, out_qtype, out_d, out_qm, out_t,
+                         out_levels, reinterpret_cast<const int8_t*>(epi_table));
+    return qvit_launch_status();
+  }
   const int64_t grid = std::min<int64_t>(nblk, 2 * (int64_t)qvit_device_cus());  // two resident workgroups per CU
   if (out_mode == QVIT_ATT_F32)
     hipLaunchKernelGGL(attn_split_kernel<0>, dim3((unsigned)grid), dim3(256), 0, stream, hi, lo, (int)N, (int)H,

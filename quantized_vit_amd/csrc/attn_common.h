@@ -14,7 +14,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 
 constexpr int HD = 64;          // head dim of the fused and split kernels; the first 64 columns of a wider head
-constexpr int HD80 = 80;        // the other head dim of attn_kernel (fp32 output) and the backward kernels (ViT-Huge/14)
+constexpr int HD80 = 80;        // the other head dim of attn_kernel (fp32 output), the split and the backward kernels (ViT-Huge/14)
 constexpr int KB = 32;          // keys per block
 constexpr int IMG = KB * HD * 2;       // one fp16 image of a key block: 4 KiB
 // Head dim 80 = 64 + 16. A key block's image keeps its first 64 columns in the 128-B-row image above, same
@@ -277,7 +277,8 @@ struct EpiLds {
 
 // 4x4 transpose between the lane groups g (lanes 16g..16g+15) and the 4 registers: afterwards lane g
 // holds what lane k held in register g, as w[k] (two permlane32 swaps, then two permlane16 swaps).
-QVIT_DEV void transpose_groups(uint32_t (&w)[4]) {
+template <int K>
+QVIT_DEV void transpose_groups(uint32_t (&w)[K]) {  // w[0 .. 3]; a head-dim-80 caller's fifth word stays
   auto a = __builtin_amdgcn_permlane32_swap(w[0], w[2], false, false);
   auto b = __builtin_amdgcn_permlane32_swap(w[1], w[3], false, false);
   w[0] = a[0]; w[2] = a[1]; w[1] = b[0]; w[3] = b[1];
@@ -289,13 +290,16 @@ QVIT_DEV void transpose_groups(uint32_t (&w)[4]) {
 // Normalise and write a wave's query tiles: fp32 rows, or the next layer's int8 codes. With st16 the
 // codes of a row leave as one 16-B store per lane (lane group g: columns 16g .. 16g+15 of the head).
 // Tile i of the wave is query tile qtile0 + tstride * i of the group starting at q0.
+// Head dim 80, int8: a head's 80 B start at a multiple of 16, so the first 64 columns take the same path and the
+// fifth slice (columns 64 + 4 g .. + 3 of lane group g) leaves as one 4-B store per lane either way.
 template <int OUT, int T, int D = HD>
 QVIT_DEV void attend_store(const bool (&tv)[T], const float (&l)[T], const f4 (&o)[T][D / 16], int qtile0, int tstride,
                            int q0, int N, int b, int h, float in_scale, void* out, int64_t ldo, const QParams& qp,
                            const EpiLds& tb, bool st16) {
   const int lane = threadIdx.x & 63;
   const int fr = lane & 15, g = lane >> 4;
-  static_assert(D == HD || (D == HD80 && OUT == 0), "the int8 epilogue is for head dim 64");
+  static_assert(D == HD || D == HD80, "head dim 64 or 80");
+  constexpr int ND = D / 16;
 #pragma unroll
   for (int i = 0; i < T; ++i) {
     if (!tv[i]) continue;  // wave-uniform
@@ -311,19 +315,19 @@ QVIT_DEV void attend_store(const bool (&tv)[T], const float (&l)[T], const f4 (&
       }
       continue;
     }
-    uint32_t wd[4];
+    uint32_t wd[ND];
     if (tb.ent != nullptr) {
-      float v[4][4];
-      uint2 e[4][4];
+      float v[ND][4];
+      uint2 e[ND][4];
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt)
+      for (int dt = 0; dt < ND; ++dt)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           v[dt][j] = o[i][dt][j] * inv;
           e[dt][j] = *epi_entry(tb.ent, v[dt][j], tb.c0, tb.inv_w, tb.top);
         }
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
+      for (int dt = 0; dt < ND; ++dt) {
         epi_select_byte<0>(wd[dt], v[dt][0], __uint_as_float(e[dt][0].x), e[dt][0].y);
         epi_select_byte<1>(wd[dt], v[dt][1], __uint_as_float(e[dt][1].x), e[dt][1].y);
         epi_select_byte<2>(wd[dt], v[dt][2], __uint_as_float(e[dt][2].x), e[dt][2].y);
@@ -331,7 +335,7 @@ QVIT_DEV void attend_store(const bool (&tv)[T], const float (&l)[T], const f4 (&
       }
     } else {
 #pragma unroll
-      for (int dt = 0; dt < 4; ++dt) {
+      for (int dt = 0; dt < ND; ++dt) {
         const f4 v = o[i][dt] * inv;
         float k[4];
         bool need[4];
@@ -348,7 +352,9 @@ QVIT_DEV void attend_store(const bool (&tv)[T], const float (&l)[T], const f4 (&
         wd[dt] = word;
       }
     }
-    int8_t* dst = reinterpret_cast<int8_t*>(out) + row * ldo + h * HD;
+    int8_t* dst = reinterpret_cast<int8_t*>(out) + row * ldo + h * D;
+    if constexpr (D == HD80)
+      if (q < N) *reinterpret_cast<uint32_t*>(dst + 64 + 4 * g) = wd[4];
     if (st16) {
       transpose_groups(wd);
       if (q < N) *reinterpret_cast<uint4*>(dst + 16 * g) = make_uint4(wd[0], wd[1], wd[2], wd[3]);

@@ -37,6 +37,9 @@ typedef int v4i __attribute__((ext_vector_type(4)));
 // internal epilogue of qvit_gemm_resid_ln: QVIT_EPI_F32_RESID (stores written through, sc1) and, behind the last
 // of a row block's tiles, LayerNorm + the next layer's activation quantizer of that block's rows
 constexpr int EPI_RESID_LN = 16;
+// internal epilogue of qvit_gemm_qkv_split_hd at head_dim 80: QVIT_EPI_QKV_SPLIT with 80-column head planes
+constexpr int EPI_QKV_SPLIT80 = 17;
+constexpr bool is_qkv_split(int epi) { return epi == QVIT_EPI_QKV_SPLIT || epi == EPI_QKV_SPLIT80; }
 
 constexpr int BN = 256;    // weight rows per tile
 constexpr int BK = 64;     // k per stage
@@ -990,15 +993,18 @@ __global__ __launch_bounds__((Geo<WFMT, WM>::NT), (Geo<WFMT, WM>::MIN_BLOCKS)) v
         }
       }
       }
-    } else if (EPI == QVIT_EPI_QKV_SPLIT) {
+    } else if (is_qkv_split(EPI)) {
       // fp16 hi/lo planes: 8 lanes per 64-column head-plane row, 8 columns (16 B of hi, 16 B of lo) each
+      // (80-column planes: the wave's 64 columns straddle heads, a lane's 8 never do, 80 % 8 == 0; N % 64 may be
+      // anything, so a lane checks its own columns, N % 8 == 0: all valid or none)
+      constexpr int PD = EPI == EPI_QKV_SPLIT80 ? 80 : 64;
       int* stg = reinterpret_cast<int*>(epi_lds + wave * EPI_WAVE_BYTES);
       const int prow = el >> 3, pcol = 8 * (el & 7);
       const int nw = n0 + 64 * wn;  // the wave's head plane (N % 64 == 0: all valid or none)
       float bb[8];
 #pragma unroll
       for (int j = 0; j < 8; ++j) bb[j] = has_bias ? bias_l[nw - n0 + pcol + j] : 0.f;
-      const int64_t pstride = (int64_t)ep.seq * 64;
+      const int64_t pstride = (int64_t)ep.seq * PD;
 #pragma unroll
       for (int sr = 0; sr < 8; ++sr) {
         __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -1013,12 +1019,16 @@ __global__ __launch_bounds__((Geo<WFMT, WM>::NT), (Geo<WFMT, WM>::MIN_BLOCKS)) v
           const int m = m0 + 128 * wm + 16 * sr + row;
           const v4i a0 = *reinterpret_cast<const v4i*>(stg + row * EPI_LD + pcol);
           const v4i a1 = *reinterpret_cast<const v4i*>(stg + row * EPI_LD + pcol + 4);
-          if (m < M && nw < N) {
+          if (m < M && (PD == 64 ? nw : nw + pcol) < N) {
             int bimg = (int)((float)m * ep.inv_seq);
             bimg -= (bimg * ep.seq > m) ? 1 : 0;
             bimg += ((bimg + 1) * ep.seq <= m) ? 1 : 0;
             const int tok = m - bimg * ep.seq;
-            const int64_t e = ((int64_t)bimg * (N >> 6) + (nw >> 6)) * pstride + (int64_t)tok * 64 + pcol;
+            int64_t e;
+            if constexpr (PD == 64)
+              e = ((int64_t)bimg * (N >> 6) + (nw >> 6)) * pstride + (int64_t)tok * 64 + pcol;
+            else
+              e = ((int64_t)bimg * (N / PD) + (nw + pcol) / PD) * pstride + (int64_t)tok * PD + (nw + pcol) % PD;
             uint32_t hw[4], lw[4];
 #pragma unroll
             for (int j = 0; j < 8; j += 2) {
@@ -1146,7 +1156,7 @@ int launch(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, i
   const int64_t span = (int64_t)0xFFFFFFFF - K;
   int64_t rows = span / lda / G::BM * G::BM;
   if (rows < G::BM || npad * (K / (WFMT == QVIT_W4 && RW != 2 ? 2 : 1)) > span) return QVIT_EINVAL;
-  if (EPI == QVIT_EPI_QKV_SPLIT && rows < M) return QVIT_EINVAL;  // its row -> (image, token) map is global
+  if (is_qkv_split(EPI) && rows < M) return QVIT_EINVAL;  // its row -> (image, token) map is global
   const int64_t esize = (EPI == QVIT_EPI_I8 || EPI == QVIT_EPI_I8_GELU) ? 1 : 4;
   for (int64_t m0 = 0; m0 < M; m0 += rows) {
     const int64_t mc = (M - m0 < rows) ? M - m0 : rows;
@@ -1156,7 +1166,7 @@ int launch(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, i
     const int64_t need = (ntiles + 7) / 8 * 8;
     if (grid > need) grid = need;
     if (grid < 8) grid = 8;
-    void* Cc = reinterpret_cast<int8_t*>(C) + (EPI == QVIT_EPI_QKV_SPLIT ? 0 : m0 * ldc * esize);
+    void* Cc = reinterpret_cast<int8_t*>(C) + (is_qkv_split(EPI) ? 0 : m0 * ldc * esize);
     EpiArgs epc = ep;
     if (EPI == EPI_RESID_LN) {  // this chunk's row blocks and code rows
       epc.ln_cnt = ep.ln_cnt + m0 / G::BM;
@@ -1295,12 +1305,23 @@ extern "C" int qvit_gemm_resid_ln(const int8_t* A, int64_t M, int64_t K, int64_t
 
 QVIT_GEMM_STAMP_READER  // diag_stamps.h: exists only in -DQVIT_GEMM_STAMPS builds
 
-extern "C" int qvit_gemm_qkv_split(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, int wfmt,
-                                   int64_t N, int64_t npad, const float* d_act, const float* d_wt, const float* bias,
-                                   int64_t seq, float in_scale, void* qkv_hi, void* qkv_lo, hipStream_t stream) {
+// qvit_gemm_qkv_split and qvit_gemm_qkv_split_hd: one list of checks, head_dim 64 for the former
+template <int EPI>
+static int qkv_split_launch(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, int wfmt, int64_t N,
+                            int64_t npad, void* qkv_hi, const EpiArgs& ep, hipStream_t stream) {
+  if (wfmt == QVIT_W4) return launch<QVIT_W4, EPI>(A, M, K, lda, Wp, N, npad, qkv_hi, N, ep, stream);
+  if (wfmt == QVIT_W4R) return launch<QVIT_W4, EPI, 1>(A, M, K, lda, Wp, N, npad, qkv_hi, N, ep, stream);
+  if (wfmt == QVIT_W8R) return launch<QVIT_W4, EPI, 2>(A, M, K, lda, Wp, N, npad, qkv_hi, N, ep, stream);
+  return launch<QVIT_W8, EPI>(A, M, K, lda, Wp, N, npad, qkv_hi, N, ep, stream);
+}
+
+static int qkv_split(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, int wfmt, int64_t N,
+                     int64_t npad, const float* d_act, const float* d_wt, const float* bias, int64_t seq,
+                     int64_t head_dim, float in_scale, void* qkv_hi, void* qkv_lo, hipStream_t stream) {
   if (!A || !Wp || !qkv_hi || !qkv_lo || !d_act || !d_wt) return QVIT_ENULL;
   if (wfmt != QVIT_W4 && wfmt != QVIT_W4R && wfmt != QVIT_W8R && wfmt != QVIT_W8) return QVIT_EINVAL;
-  if (M < 0 || K <= 0 || K % KTILE || lda < K || N <= 0 || N % 64 || npad < N || npad % BN) return QVIT_EINVAL;
+  if (head_dim != 64 && head_dim != 80) return QVIT_EINVAL;
+  if (M < 0 || K <= 0 || K % KTILE || lda < K || N <= 0 || N % head_dim || npad < N || npad % BN) return QVIT_EINVAL;
   if (M > INT32_MAX / 2 || npad > INT32_MAX / 2 || K > (1 << 24)) return QVIT_EINVAL;
   if (seq <= 0 || seq > (1 << 20) || M % seq || !(in_scale > 0.f)) return QVIT_EINVAL;
   if (wfmt != QVIT_W8 && K > 65536) return QVIT_EINVAL;
@@ -1310,11 +1331,20 @@ extern "C" int qvit_gemm_qkv_split(const int8_t* A, int64_t M, int64_t K, int64_
   if (M == 0) return QVIT_OK;
   EpiArgs ep{d_act, d_wt, bias, 0, nullptr, nullptr, nullptr, 0, nullptr, (int)seq, 1.0f / (float)seq, in_scale,
              reinterpret_cast<_Float16*>(qkv_lo)};
-  if (wfmt == QVIT_W4)
-    return launch<QVIT_W4, QVIT_EPI_QKV_SPLIT>(A, M, K, lda, Wp, N, npad, qkv_hi, N, ep, stream);
-  if (wfmt == QVIT_W4R)
-    return launch<QVIT_W4, QVIT_EPI_QKV_SPLIT, 1>(A, M, K, lda, Wp, N, npad, qkv_hi, N, ep, stream);
-  if (wfmt == QVIT_W8R)
-    return launch<QVIT_W4, QVIT_EPI_QKV_SPLIT, 2>(A, M, K, lda, Wp, N, npad, qkv_hi, N, ep, stream);
-  return launch<QVIT_W8, QVIT_EPI_QKV_SPLIT>(A, M, K, lda, Wp, N, npad, qkv_hi, N, ep, stream);
+  if (head_dim == 80) return qkv_split_launch<EPI_QKV_SPLIT80>(A, M, K, lda, Wp, wfmt, N, npad, qkv_hi, ep, stream);
+  return qkv_split_launch<QVIT_EPI_QKV_SPLIT>(A, M, K, lda, Wp, wfmt, N, npad, qkv_hi, ep, stream);
+}
+
+extern "C" int qvit_gemm_qkv_split(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, int wfmt,
+                                   int64_t N, int64_t npad, const float* d_act, const float* d_wt, const float* bias,
+                                   int64_t seq, float in_scale, void* qkv_hi, void* qkv_lo, hipStream_t stream) {
+  return qkv_split(A, M, K, lda, Wp, wfmt, N, npad, d_act, d_wt, bias, seq, 64, in_scale, qkv_hi, qkv_lo, stream);
+}
+
+extern "C" int qvit_gemm_qkv_split_hd(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, int wfmt,
+                                      int64_t N, int64_t npad, const float* d_act, const float* d_wt,
+                                      const float* bias, int64_t seq, int64_t head_dim, float in_scale, void* qkv_hi,
+                                      void* qkv_lo, hipStream_t stream) {
+  return qkv_split(A, M, K, lda, Wp, wfmt, N, npad, d_act, d_wt, bias, seq, head_dim, in_scale, qkv_hi, qkv_lo,
+                   stream);
 }

@@ -210,7 +210,7 @@ class ViTAttention(nn.Module):
 
     def split_ok(self, p_qkv) -> bool:
         """The fused block can take the split-operand path (qvit_gemm_qkv_split -> qvit_attention_split)."""
-        return (self.head_dim == 64 and p_qkv.n == 3 * self.num_heads * 64
+        return (self.head_dim in (64, 80) and p_qkv.n == 3 * self.num_heads * self.head_dim
                 and not (self.training and self.attn_drop.p > 0))
 
     def core_hip(self, qkv: torch.Tensor, B: int, N: int, out: torch.Tensor, out_mode: int = _lib.ATT_F32,
@@ -402,7 +402,8 @@ class Block(nn.Module):
                                         code_table=epilogue_table(p_qkv, _lib.EPI_I8))
         trace_codes(a.qkv, codes, C)
         p_proj = a.proj.quant_plan()
-        if (a.split_ok(p_qkv) and N <= _lib.QKV_ATT_MAX_N and p_qkv.wfmt == _lib.W4 and p_qkv.kpad <= 65536
+        if (a.split_ok(p_qkv) and a.head_dim == 64 and N <= _lib.QKV_ATT_MAX_N and p_qkv.wfmt == _lib.W4
+                and p_qkv.kpad <= 65536
                 and p_qkv.kpad % 256 == 0 and a.num_heads * 64 <= _lib.QKV_ATT_MAX_C):
             # qkv projection + attention + proj's activation quantizer in one kernel (q/k/v stay on chip)
             # (last: compact [B*nt, kpad], the wanted queries only)
@@ -437,11 +438,11 @@ class Block(nn.Module):
             lo = torch.empty(M * p_qkv.n, dtype=torch.float16, device=x.device)
             wimg, wfmt = p_qkv.gemm_weights()
             _lib.gemm_qkv_split(codes, M, p_qkv.kpad, wimg, wfmt, p_qkv.n, p_qkv.npad, p_qkv.d_act,
-                                p_qkv.d_wt, p_qkv.bias_pad, N, in_scale, hi, lo)
+                                p_qkv.d_wt, p_qkv.bias_pad, N, in_scale, hi, lo, head_dim=a.head_dim)
             codes = torch.empty((M, p_proj.kpad), dtype=torch.int8, device=x.device)
-            if p_proj.kpad != a.num_heads * 64:
-                codes[:, a.num_heads * 64:].zero_()
-            _lib.attention_split(hi, lo, B, N, a.num_heads, 64, a.scale, codes, _lib.ATT_I8, in_scale,
+            if p_proj.kpad != a.num_heads * a.head_dim:
+                codes[:, a.num_heads * a.head_dim:].zero_()
+            _lib.attention_split(hi, lo, B, N, a.num_heads, a.head_dim, a.scale, codes, _lib.ATT_I8, in_scale,
                                  p_proj.qtype, p_proj.d_act, p_proj.qm_act, p_proj.t_act,
                                  epi_table=epilogue_table(p_proj, _lib.EPI_I8))
             trace_codes(a.proj, codes, p_proj.k)
@@ -454,7 +455,7 @@ class Block(nn.Module):
             qkv = qkv[:, :p_qkv.n]
         if a.hip_ok(qkv) and a.head_dim == 64:
             # attention core + proj's activation quantizer in one kernel: int8 codes for the proj GEMM
-            # (head_dim 80: the fp32 core below, then proj's quantizer on its own)
+            # (head_dim 80 reaches this point only when split_ok is false: the fp32 core below, then proj's quantizer)
             codes = torch.empty((M, p_proj.kpad), dtype=torch.int8, device=x.device)
             if p_proj.kpad != a.num_heads * 64:
                 codes[:, a.num_heads * 64:].zero_()

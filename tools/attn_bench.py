@@ -1,7 +1,8 @@
 """Times qvit_attention on the ViT-B/16 b256 shape (B=256, N=197, H=12, hd=64) against torch's fp32
 bmm + softmax + bmm sequence on the same qkv, with HIP events (median over iters).
---hd 80 (ViT-Huge/14: --B 64 --N 257 --H 16 --hd 80) times the fp32-output kernel against the torch ops, the two
-alternated in one process, with the peak allocation of each."""
+--hd 80 (ViT-Huge/14: --B 64 --N 257 --H 16 --hd 80) times the fp32-output kernel, the split kernel (fp32 and int8
+output, on planes [B][3H][N][80] of the same data) and the torch ops, alternated in one process, with the peak
+allocation of each."""
 import argparse
 import os
 import sys
@@ -39,6 +40,19 @@ def head_dim_ab(dev, B, N, H, hd, iters):
         return (at @ x[2]).transpose(1, 2).reshape(B * N, H * hd)
 
     routes = {"qvit_attention f32": lambda: _lib.attention(qkv, B, N, H, hd, scale, out), "torch fp32": torch_ref}
+    if hd == 80:   # the split kernel on the same values: head-major fp16 hi/lo planes, in_scale 1
+        planes = lambda t: t.reshape(B, N, 3 * H, hd).permute(0, 2, 1, 3).contiguous().reshape(-1)
+        hi, lo = planes(qkv.half()), planes((qkv - qkv.half().float()).half())
+        codes = torch.empty(B * N, H * hd, dtype=torch.int8, device=dev)
+        d, qm = torch.tensor([2.0 / 127], device=dev), torch.tensor([2.0], device=dev)
+        t = torch.tensor([1.0], device=dev)
+        from quantized_vit_amd.quant_layers import epilogue_table_geometry, saturation_level
+        geo = epilogue_table_geometry(_lib.QT_NONLINEAR, 2.0 / 127, 2.0, 1.0,
+                                      saturation_level(_lib.QT_NONLINEAR, 2.0 / 127, 2.0, 1.0), False)
+        table = _lib.epi_table_build(_lib.EPI_I8, _lib.QT_NONLINEAR, d, qm, t, 0, *geo, dev)   # as the model does
+        routes["split f32"] = lambda: _lib.attention_split(hi, lo, B, N, H, hd, scale, out)
+        routes["split i8"] = lambda: _lib.attention_split(hi, lo, B, N, H, hd, scale, codes, _lib.ATT_I8, 1.0,
+                                                          _lib.QT_NONLINEAR, d, qm, t, epi_table=table)
     times = {k: [] for k in routes}
     for fn in routes.values():   # warm both routes before the first timed round
         timeit(fn, iters)
@@ -63,7 +77,7 @@ def main():
     ap.add_argument("--B", type=int, default=256)
     ap.add_argument("--N", type=int, default=197)
     ap.add_argument("--H", type=int, default=12)
-    ap.add_argument("--hd", type=int, default=64, choices=(64, 80), help="head dim (80: fp32 output and torch only)")
+    ap.add_argument("--hd", type=int, default=64, choices=(64, 80), help="head dim (80: fp32-input, split and torch routes)")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--lib", default="", help="load this library build instead (diagnostic variants)")
     ap.add_argument("--split-only", action="store_true")
