@@ -31,6 +31,8 @@
  *   qvit_gemm_wgrad           the backward of quant_layers.py:499's F.linear w.r.t. the quantized weight on the
  *                             integer path: fp32 grad_out^T x int8 activation codes on bf16 MFMA (the same exact
  *                             three-term split); the input's gradient is qvit_gemm_wonly on transposed codes.
+ *   qvit_col2im_quant_backward  the backward of quant_layers.py:575-587 (QuantizeConv2d.forward) w.r.t. its input behind
+ *                             the im2col lowering: col2im of the patch-row gradient fused with quantize_act's backward.
  *   qvit_conv_wonly           quant_layers.py:575-587 (QuantizeConv2d.forward, WEIGHT_ONLY) and quant_ultra.py:85-89
  *                             (Conv2d_Q.forward): the same contraction as an implicit GEMM over the NCHW input
  *                             (patches gathered in the kernel), NCHW fp32 out — F.conv2d(x, quantize_weight(W), b).
@@ -392,6 +394,50 @@ int64_t qvit_gemm_wgrad_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int qvit_gemm_wgrad(const float* G, int64_t M, int64_t N, int64_t ldg, const int8_t* A, int64_t K, int64_t lda,
                     const float* d_act, float* dW, int64_t ldw, void* workspace, int64_t workspace_bytes,
                     hipStream_t stream);
+
+/*
+ * The backward GEMMs of QuantizeConv2d on the integer path are those of QuantizeLinear over the patch rows the
+ * forward contracted (qvit_im2col_quant_i8 + qvit_gemm): M = B OH OW rows of K = C kh kw columns.
+ *   wgrad  qvit_gemm_wgrad on G2 (the [M][N] row view of the output gradient) and the im2col codes, which
+ *          qvit_im2col_quant_i8 recomputes; dW [N][K] is nn.Conv2d.weight.grad's layout. No new entry point.
+ *   dgrad  P = G2 (d_wt k_w) on qvit_gemm_wonly as for QuantizeLinear, then qvit_col2im_quant_backward: the adjoint
+ *          of im2col (col2im) and the backward of quantize_act in one pass over the image,
+ *            grad_xq[b][c][y][x] = sum over ky ascending, inside it kx ascending, with
+ *                                  (y + ph - ky dh) % sh == 0, oy = (y + ph - ky dh) / sh in [0, OH) (x axis alike)
+ *                                  of P[(b OH + oy) OW + ox][(c kh + ky) kw + kx],
+ *          then (grad_x, grad_scalars) exactly as qvit_quant_backward gives them for (x, grad_out = grad_xq), dge_k 0.
+ *   P      : fp32 [M][ldp], K valid columns in the order of qvit_im2col_quant_i8; columns [K, ldp) are never read.
+ *   x      : fp32 NCHW [B][C][H][W] contiguous, the layer's input; NULL selects the fold-only mode: grad_x receives
+ *            grad_xq itself, and qtype, the quantizer scalars, the clip values, grad_scalars and the workspace are
+ *            not looked at (all may be 0 / NULL). For layers without an activation quantizer.
+ *   grad_x : fp32 NCHW [B][C][H][W] contiguous. Must not alias P (an element is written while other threads still
+ *            read rows of P) nor x.
+ *   grad_scalars : float[3] as qvit_quant_backward. workspace: qvit_col2im_quant_backward_workspace_bytes(...)
+ *            bytes, 8-byte aligned, contents irrelevant (one partial per workgroup, at most 1024, folded in a fixed
+ *            order by a second launch).
+ * A gather: every image element adds its own taps in the order above in fp32, starting from 0. No atomics, two
+ * calls give the same bits; an element that no output position reads is exactly 0; a tap on the zero padding has no
+ * image element and contributes nothing. A NaN in P reaches the elements that tap it (where the clip lets grad_out
+ * through) and the sums.
+ * Arms (the same bits wherever both apply): groups of four consecutive x read one 16-byte chunk of a row of P per
+ * ky tap when pw == 0, dw == 1, kw % 4 == 0, sw % 4 == 0, sw >= kw, W % 4 == 0, ldp % 4 == 0 and P, x, grad_x are
+ * 16-byte aligned (the patch embedding: k == s, p == 0); otherwise one element per thread, any geometry, any 4-byte
+ * aligned pointers. Offsets are 32-bit while M ldp < 2^31 and B C H W < 2^31, else 64-bit.
+ * Sizes: groups == 1, zero padding; B, C <= 2^20; H, W, sh, sw, ph, pw <= 2^16; kh, kw, dh, dw <= 1024; K <= 2^24;
+ * K <= ldp <= 2^24; B C H W, M and M ldp < 2^40; else QVIT_EINVAL (the geometry and the image totals also from the
+ * query). B == 0 writes three zeros (nothing in the fold-only mode).
+ * Order of the checks: NULL (P, grad_x; with x also grad_scalars, d_quant, q_m, workspace); with x the qtype
+ * (QVIT_EINVAL), then t_quant for the nonlinear quantizer (QVIT_ENULL); the upper bounds, the geometry
+ * (qvit_im2col_quant_i8's rules) and the totals, then ldp (QVIT_EINVAL); with x the workspace size (QVIT_EINVAL);
+ * 4-byte alignment of P, x, grad_x and 8-byte alignment of the workspace (QVIT_EALIGN).
+ */
+int64_t qvit_col2im_quant_backward_workspace_bytes(int64_t B, int64_t C, int64_t H, int64_t W, int kh, int kw,
+                                                   int sh, int sw, int ph, int pw, int dh, int dw);
+int qvit_col2im_quant_backward(const float* P, int64_t ldp, const float* x, int64_t B, int64_t C, int64_t H,
+                               int64_t W, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int qtype,
+                               const float* d_quant, const float* q_m, const float* t_quant, float clip_lo,
+                               float clip_hi, float* grad_x, float* grad_scalars /* [3] */, void* workspace,
+                               int64_t workspace_bytes, hipStream_t stream);
 
 /*
  * Weight-only convolution (QuantizeConv2d.forward, quant_layers.py:575-587, quant_mode WEIGHT_ONLY; UltraNet's

@@ -82,6 +82,8 @@ _SIGNATURES = {
                       _c_p, _i32, _c_p, _c_p],
     "qvit_gemm_wonly": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i64, _c_p, _i64, _c_p],
     "qvit_gemm_wgrad": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i64, _c_p, _i64, _c_p],
+    "qvit_col2im_quant_backward": [_c_p, _i64, _c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                   _i32, _i32, _c_p, _c_p, _c_p, _f32, _f32, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_conv_wonly": [_c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_p, _i32,
                         _i64, _i64, _i64, _c_p, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_conv_wonly_bn_act": [_c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_p,
@@ -133,6 +135,8 @@ INT64_FUNCS = {
     "qvit_gelu_quant_backward_workspace_bytes": [_i64],
     "qvit_attention_backward_workspace_bytes": [_i64, _i64, _i64],
     "qvit_gemm_wgrad_workspace_bytes": [_i64, _i64, _i64],
+    "qvit_col2im_quant_backward_workspace_bytes": [_i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                                   _i32],
     "qvit_ultra_weight_quant_backward_workspace_bytes": [_i64],
     "qvit_conv_wgrad_workspace_bytes": [_i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
     "qvit_bn_stats_workspace_bytes": [_i64, _i64, _i64, _i64],
@@ -601,6 +605,53 @@ def conv_out_hw(H: int, W: int, kernel_size, stride, padding, dilation) -> Tuple
     padded image smaller than the dilated kernel is the library's to reject: it checks the extents itself.)"""
     (kh, kw), (sh, sw), (ph, pw), (dh, dw) = kernel_size, stride, padding, dilation
     return (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+
+
+def col2im_quant_backward(P: torch.Tensor, x: Optional[torch.Tensor], xshape, kernel_size, stride, padding, dilation,
+                          qtype: int = QT_LINEAR, d: Optional[torch.Tensor] = None, qm: Optional[torch.Tensor] = None,
+                          t: Optional[torch.Tensor] = None, clip_lo: float = 0.0, clip_hi: float = 0.0,
+                          grad_x: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None):
+    """col2im of the patch-row gradient P (fp32 [B*OH*OW, >= C*kh*kw] rows in im2col_quant_i8's column order, any
+    row stride) into an image of shape `xshape`, fused with the backward of the activation quantizer over the
+    layer's input x (qvit_col2im_quant_backward). Returns (grad_x, scalars) as quant_backward does, on the device
+    with no host sync. Fold-only form: x = None returns (grad_xq, None) and takes no quantizer arguments. `grad_x`
+    (fp32, contiguous, of shape xshape) must not share memory with P; `workspace`: float64, at least the query's
+    bytes (contents irrelevant)."""
+    _require_gpu(P, "P")
+    B, C, H, W = (int(v) for v in xshape)
+    (kh, kw), (sh, sw), (ph, pw), (dh, dw) = kernel_size, stride, padding, dilation
+    geo = (B, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw)
+    OH, OW = conv_out_hw(H, W, kernel_size, stride, padding, dilation)
+    K = C * kh * kw
+    if P.dim() != 2 or P.shape[0] != B * OH * OW or P.shape[1] < K:
+        raise QvitError(f"col2im_quant_backward: P of shape {tuple(P.shape)} for {B * OH * OW} patch rows of {K}")
+    if P.dtype != torch.float32 or P.stride(1) != 1 or (P.shape[0] > 1 and P.stride(0) < K):
+        P = P.detach().float().contiguous()
+    dev = P.device
+    if x is not None:
+        _require_gpu(x, "input")
+        x = x.detach()
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.float().contiguous()
+        if tuple(x.shape) != (B, C, H, W):
+            raise QvitError(f"col2im_quant_backward: input of shape {tuple(x.shape)} for an image of {(B, C, H, W)}")
+    if grad_x is None:
+        grad_x = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
+    assert grad_x.is_cuda and grad_x.dtype == torch.float32 and grad_x.is_contiguous() and \
+        tuple(grad_x.shape) == (B, C, H, W)
+    lib = load()
+    scalars, nbytes = None, 0
+    if x is not None:
+        nbytes = int(lib.qvit_col2im_quant_backward_workspace_bytes(*geo))
+        workspace = _workspace(nbytes, "qvit_col2im_quant_backward_workspace_bytes", workspace, dev)
+        nbytes = workspace.numel() * workspace.element_size()
+        scalars = torch.empty(3, dtype=torch.float32, device=dev)
+    ldp = P.stride(0) if P.shape[0] > 1 else max(P.shape[1], 1)
+    _check(lib.qvit_col2im_quant_backward(_ptr(P), ldp, _ptr(x), *geo, qtype, _ptr(d), _ptr(qm), _ptr(t),
+                                          float(clip_lo), float(clip_hi), _ptr(grad_x), _ptr(scalars),
+                                          _ptr(workspace) if x is not None else None, nbytes, _stream(dev)),
+           "qvit_col2im_quant_backward")
+    return grad_x, scalars
 
 
 def conv_wonly(x: torch.Tensor, kernel_size, stride, padding, dilation, packed: torch.Tensor, wfmt: int, N: int,

@@ -22,7 +22,8 @@ GEMM instead. CPU tensors are rejected: the product has no CPU fallback.
 Autograd: a layer called with gradients enabled, and an input or a parameter that requires grad, records
 one autograd node around the very same forward (bit-identical output). Its backward runs the two GEMM
 gradients (QuantizeLinear: on the integer codes, qvit_gemm_wonly on the transposed weight codes and
-qvit_gemm_wgrad on the activation codes, see BACKWARD_GEMM; otherwise torch's fp32 GEMM / convolution) and the
+qvit_gemm_wgrad on the activation codes, see BACKWARD_GEMM; QuantizeConv2d: the same two kernels over the im2col
+patch rows plus qvit_col2im_quant_backward, see CONV_BACKWARD_GEMM; otherwise torch's fp32 GEMM / convolution) and the
 reference's quantizer backwards (quant_layers.py:71-125, 163-205) as
 one fused HIP pass each (qvit_quant_backward): grad_x plus the gradients of d_quant, q_m and t_quant through
 a deterministic reduction. SymQuantizerLinear / SymQuantizerNonLinear / DGEQuantizer expose the same pass at
@@ -261,6 +262,29 @@ def _backward_gemm_ops() -> tuple:
         return _BACKWARD_GEMM_OPS[BACKWARD_GEMM]
     except KeyError:
         raise ValueError(f"BACKWARD_GEMM = {BACKWARD_GEMM!r}: expected hip, torch, dgrad or wgrad") from None
+
+
+# The backward GEMMs of QuantizeConv2d (behind F.conv2d's backward), a switch of its own: "hip" runs both on the
+# project's kernels wherever the layer is eligible (groups 1, zero padding, packed codes), wgrad as qvit_gemm_wgrad
+# on the recomputed im2col codes (integer path), dgrad as qvit_gemm_wonly on the transposed weight codes followed by
+# qvit_col2im_quant_backward (the fold and the activation quantizer's backward in one pass); "torch" keeps both on
+# torch.nn.grad's convolutions; "dgrad" / "wgrad" select one op. Unset (None: not a value the variable can name), a layer takes the route that was
+# faster where it was measured: both ops on the kernels where no two kernel taps reach the
+# same input element (stride >= dilated kernel extent on both axes: the patch embeddings, 2.1x to 9.6x the library),
+# both on the library where taps overlap (P is then kh kw / (sh sw) times the image; the one 3 x 3 stride-1 layer
+# measured ran at a third of the library's speed on either op). QVIT_CONV_BWD_GEMM sets it.
+CONV_BACKWARD_GEMM = os.environ.get("QVIT_CONV_BWD_GEMM")
+if CONV_BACKWARD_GEMM is not None and CONV_BACKWARD_GEMM not in _BACKWARD_GEMM_OPS:
+    raise ValueError(f"QVIT_CONV_BWD_GEMM={CONV_BACKWARD_GEMM!r}: expected hip, torch, dgrad or wgrad")
+
+
+def _conv_backward_gemm_ops(overlap: bool) -> tuple:
+    if CONV_BACKWARD_GEMM is None:
+        return () if overlap else ("dgrad", "wgrad")
+    try:
+        return _BACKWARD_GEMM_OPS[CONV_BACKWARD_GEMM]
+    except KeyError:
+        raise ValueError(f"CONV_BACKWARD_GEMM = {CONV_BACKWARD_GEMM!r}: expected hip, torch, dgrad or wgrad") from None
 
 
 @dataclass
@@ -659,13 +683,35 @@ class QuantizeMixin:
         raise NotImplementedError
 
     def _backward_gemm_routes(self, plan: QuantPlan, need_xq: bool, need_wq: bool) -> Tuple[bool, bool]:
-        """(dgrad, wgrad) on the HIP kernels (QuantizeLinear only; every other layer keeps the library)."""
+        """(dgrad, wgrad) on the HIP kernels (BACKWARD_GEMM for QuantizeLinear, CONV_BACKWARD_GEMM for
+        QuantizeConv2d)."""
         return False, False
 
     def _gemm_grads_hip(self, plan: QuantPlan, xf: torch.Tensor, x_q: Optional[torch.Tensor],
                         w_q: Optional[torch.Tensor], G: torch.Tensor, hip_x: bool, hip_w: bool):
-        """_gemm_grads with the ops flagged by _backward_gemm_routes on the HIP kernels."""
+        """_gemm_grads with the ops flagged by _backward_gemm_routes on the HIP kernels. A third element, when
+        returned, holds the activation quantizer's device scalars: the first is then already the gradient of the
+        layer's input (QuantizeConv2d's dgrad folds and applies that quantizer's backward in one kernel)."""
         raise NotImplementedError
+
+    def _grad_out_layout(self, G: torch.Tensor, library_op: bool) -> torch.Tensor:
+        """The fp32 output gradient as the GEMM gradients read it; `library_op`: an op on torch's route reads it."""
+        return G.contiguous()
+
+    def _dgrad_hip(self, plan: QuantPlan, G2: torch.Tensor) -> torch.Tensor:
+        """G2 @ (d_wt k_w), contiguous [M, k]: qvit_gemm_wonly on the transposed codes (rows = in-features,
+        reduction = out-features)."""
+        M = G2.shape[0]
+        packed_t, npad_t, kpad_t = plan.packed_t()
+        Gp = G2
+        if G2.shape[1] != kpad_t or G2.stride(0) % 4 or G2.data_ptr() % 16:
+            Gp = torch.zeros((M, kpad_t), dtype=torch.float32, device=G2.device)
+            Gp[:, :plan.n] = G2
+        ldy = _round_up(plan.k, 4)
+        y = torch.empty((M, ldy), dtype=torch.float32, device=G2.device)
+        if M:
+            _lib.gemm_wonly(Gp, M, kpad_t, packed_t, plan.wfmt, plan.k, npad_t, plan.d_wt, None, y)
+        return y if ldy == plan.k else y[:, :plan.k].contiguous()
 
     def _backward_plan(self, plan: QuantPlan, x: torch.Tensor, weight: torch.Tensor, G: torch.Tensor,
                        needs: tuple) -> tuple:
@@ -676,7 +722,8 @@ class QuantizeMixin:
         need_wq = need_w or any(needs[3:6])          # the weight quantizer's backward runs
         need_aq = wa and (need_x or any(needs[6:9]))   # the activation quantizer's backward runs
         need_xq = need_aq or need_x
-        G = G.detach().float().contiguous()
+        hip_x, hip_w = self._backward_gemm_routes(plan, need_xq, need_wq)
+        G = self._grad_out_layout(G.detach().float(), (need_xq and not hip_x) or (need_wq and not hip_w))
         xf = x.detach().float().contiguous()
         grad_b = None
         if need_b:
@@ -685,18 +732,20 @@ class QuantizeMixin:
         # the operands the forward contracted: quantize_weight(W), and d_act * codes (fake_quant_f32 and the int8
         # paths share quant_code) or the input itself in weight-only mode
         # (an op on its HIP route reads the integer codes instead: BACKWARD_GEMM)
-        hip_x, hip_w = self._backward_gemm_routes(plan, need_xq, need_wq)
         w_q = self.w_fakequant(plan).view_as(weight) if need_xq and not hip_x else None
         x_q = None
         if need_wq and not hip_w:
             x_q = _lib.fake_quant_f32(xf, plan.qtype, plan.d_act, plan.qm_act, plan.t_act) if wa else xf
+        act_done = ()   # QuantizeConv2d's dgrad: the activation quantizer's backward ran with it, (its scalars,)
         if hip_x or hip_w:
-            grad_xq, grad_wq = self._gemm_grads_hip(plan, xf, x_q, w_q, G, hip_x, hip_w)
+            grad_xq, grad_wq, *act_done = self._gemm_grads_hip(plan, xf, x_q, w_q, G, hip_x, hip_w)
         else:
             grad_xq, grad_wq = self._gemm_grads(plan, tuple(xf.shape), x_q, w_q, G)
         quantizers = []   # (which, grad through the quantizer, device scalars)
         grad_x = grad_xq
-        if need_aq:
+        if need_aq and act_done:
+            quantizers.append(("act", act_done[0]))
+        elif need_aq:
             grad_x, scal = _lib.quant_backward(xf, grad_xq, plan.qtype, plan.d_act, plan.qm_act, plan.t_act,
                                                self.act_clip_val[0], self.act_clip_val[1], grad_x=grad_xq)
             quantizers.append(("act", scal))
@@ -942,21 +991,6 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
             grad_wq = _lib.gemm_wgrad(G2, self._act_codes(x2, plan), plan.k, plan.d_act)
         return grad_xq, grad_wq
 
-    def _dgrad_hip(self, plan: QuantPlan, G2: torch.Tensor) -> torch.Tensor:
-        """G2 @ (d_wt k_w), contiguous [M, k]: qvit_gemm_wonly on the transposed codes (rows = in-features,
-        reduction = out-features)."""
-        M = G2.shape[0]
-        packed_t, npad_t, kpad_t = plan.packed_t()
-        Gp = G2
-        if G2.shape[1] != kpad_t or G2.stride(0) % 4 or G2.data_ptr() % 16:
-            Gp = torch.zeros((M, kpad_t), dtype=torch.float32, device=G2.device)
-            Gp[:, :plan.n] = G2
-        ldy = _round_up(plan.k, 4)
-        y = torch.empty((M, ldy), dtype=torch.float32, device=G2.device)
-        if M:
-            _lib.gemm_wonly(Gp, M, kpad_t, packed_t, plan.wfmt, plan.k, npad_t, plan.d_wt, None, y)
-        return y if ldy == plan.k else y[:, :plan.k].contiguous()
-
     def _backward_preop(self, plan: QuantPlan, eps: Optional[float], x: torch.Tensor, gamma, beta,
                         weight: torch.Tensor, codes: torch.Tensor, G: torch.Tensor, needs: tuple) -> tuple:
         """Backward of _PreOpLinearFunction: gradients for (x, gamma, beta, weight, bias, d_quant_wt, q_m_wt,
@@ -1175,6 +1209,51 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
         grad_wq = torch.nn.grad.conv2d_weight(x_q, tuple(self.weight.shape), G, *args).contiguous() \
             if need_wq else None
         return grad_xq, grad_wq
+
+    def _taps_overlap(self) -> bool:
+        """Whether two kernel taps can reach the same input element (a stride below the dilated kernel extent on an
+        axis): the patch rows then hold kh kw / (sh sw) times the image."""
+        return any(s < d * (k - 1) + 1 for k, s, d in zip(self.kernel_size, self.stride, self.dilation))
+
+    def _backward_gemm_routes(self, plan, need_xq, need_wq):
+        ops = _conv_backward_gemm_ops(self._taps_overlap())
+        if not self._int_conv_ok() or "pack_t" not in plan.extra:
+            return False, False   # groups, padding modes and levels the kernels do not take: the library, as before
+        has_codes = plan.int_path or bool(plan.extra.get("wonly"))
+        return need_xq and "dgrad" in ops and has_codes, need_wq and "wgrad" in ops and plan.int_path
+
+    def _grad_out_layout(self, G, library_op):
+        # the kernels read the [B OH OW, N] row view: a channels-last gradient (behind PatchEmbed's flatten +
+        # transpose) already is one, and only torch's convolutions get the NCHW copy
+        return G.contiguous() if library_op else G
+
+    def _gemm_grads_hip(self, plan, xf, x_q, w_q, G, hip_x, hip_w):
+        grad_xq, grad_wq = self._gemm_grads(plan, tuple(xf.shape), None if hip_w else x_q, None if hip_x else w_q, G)
+        G2 = G.permute(0, 2, 3, 1).reshape(-1, plan.n)   # a view of a channels-last G, else the one transposing copy
+        if G2.stride(1) != 1 or G2.stride(0) < plan.n:
+            # reshape merged the strides into something that is not row-major rows (an expanded gradient, as
+            # sum().backward() hands over, has strides (0, 0); a strided view keeps its inner stride): the kernels
+            # take a row stride only, so such a G is copied, as _backward_plan's contiguous() did for it before
+            G2 = G2.contiguous()
+        geometry = (self.kernel_size, self.stride, self.padding, self.dilation)
+        act_done = ()
+        if hip_x:
+            # P = G2 @ (d_wt k_w), then col2im; on a W+A layer the same pass applies quantize_act's backward
+            P = self._dgrad_hip(plan, G2)
+            if self.quant_mode == QuantizationMode.WEIGHT_AND_ACTIVATION:
+                grad_xq, scal = _lib.col2im_quant_backward(P, xf, xf.shape, *geometry, plan.qtype, plan.d_act,
+                                                           plan.qm_act, plan.t_act, *self.act_clip_val)
+                act_done = (scal,)
+            else:
+                grad_xq, _ = _lib.col2im_quant_backward(P, None, xf.shape, *geometry)
+        if hip_w:
+            # G2^T @ (d_act codes): the forward's own im2col kernel recomputes the codes it contracted
+            (kh, kw), (sh, sw), (ph, pw), (dh, dw) = geometry
+            codes = torch.empty((G2.shape[0], plan.kpad), dtype=torch.int8, device=xf.device)
+            _lib.im2col_quant_i8(xf, kh, kw, sh, sw, ph, pw, dh, dw, plan.qtype, plan.d_act, plan.qm_act, plan.t_act,
+                                 0, codes, plan.kpad)
+            grad_wq = _lib.gemm_wgrad(G2, codes, plan.k, plan.d_act).view(self.weight.shape)
+        return (grad_xq, grad_wq) + act_done
 
     def _forward_plan(self, input_: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
         if plan.int_path and self._int_conv_ok():
