@@ -19,6 +19,10 @@
  *                             layout: codes packed int4 (8 per u32) or int8, rows padded/permuted.
  *   qvit_im2col_quant_i8      quant_layers.py:575-587 (QuantizeConv2d.forward): the conv input patches
  *                             quantized to codes, K-order (c, kh, kw) = the reference weight flattening.
+ *   qvit_im2col_u8_i8 / qvit_u8_normalize_f32
+ *                             predict.py:18-19 and train.py:150-151 (transforms.ToTensor + transforms.Normalize on the
+ *                             host) folded into the step above: the image stays uint8 up to the device, and the
+ *                             normaliser (with quantize_act, for the codes) is a table of 256 entries per channel.
  *   qvit_layernorm_quant_i8   vit_model.py:193,206-207 (Block.norm1/norm2, eps 1e-6) fused with the next
  *                             QuantizeLinear's quantize_act (quant_layers.py:497-498).
  *   qvit_gemm                 quant_layers.py:499 (nn.functional.linear on fake-quant operands) as an
@@ -115,6 +119,10 @@ extern "C" {
 /* ---- qvit_attention output modes -------------------------------------------------------------- */
 #define QVIT_ATT_F32        0  /* out = softmax(q k^T * scale) v                     (fp32)          */
 #define QVIT_ATT_I8         1  /* out = q_next(softmax(q k^T * scale) v)             (int8 codes)    */
+
+/* ---- uint8 image layouts (qvit_im2col_u8_i8, qvit_u8_normalize_f32) ----------------------------- */
+#define QVIT_U8_NCHW 0  /* byte ((b C + c) H + y) W + x: a decoded batch after permute + contiguous        */
+#define QVIT_U8_NHWC 1  /* byte ((b H + y) W + x) C + c: a decoder's [B][H][W][C] output, torch.channels_last */
 
 /* Tile geometry the packed operands must be padded to. */
 #define QVIT_TILE_N  256   /* weight rows (out features) are padded to a multiple of this  */
@@ -281,6 +289,37 @@ int qvit_im2col_quant_i8(const float* x, int64_t B, int64_t C, int64_t H, int64_
                          int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                          int qtype, const float* d_quant, const float* q_m, const float* t_quant,
                          int levels, int8_t* codes, int64_t ldc, int64_t kpad, hipStream_t stream);
+
+/*
+ * The same rows from a uint8 image: codes[(b, oh, ow)][c*kh*kw + ih*kw + iw] = code_table[c][img(b, c, y, x)].
+ * With value_table[c][v] = (v / 255 - mean_c) / std_c (transforms.ToTensor + transforms.Normalize, predict.py:18-19)
+ * and code_table = qvit_quantize_act_i8(value_table), the output equals qvit_im2col_quant_i8 on the fp32 image
+ * value_table[c][img] byte for byte: an image byte has 256 values, so the table holds every code the quantizer can give.
+ *   img        : uint8, [B][C][H][W] (layout QVIT_U8_NCHW) or [B][H][W][C] (QVIT_U8_NHWC), contiguous, any alignment
+ *                (a 16-byte aligned image on the patchify geometry kw % 16 == 0, dw == 1, ph == pw == 0, W % 16 == 0,
+ *                sw % 16 == 0 is read 16 bytes at a time: NCHW, and NHWC with C == 3)
+ *   code_table : int8 [C][256], C <= 16 (held in LDS), any alignment
+ *   codes      : as qvit_im2col_quant_i8: columns [C*kh*kw, kpad) zero, columns [kpad, ldc) never touched; a tap
+ *                outside the image gives code 0 (padding comes after normalisation, as in the reference).
+ * Checks, in this order: a NULL img, code_table or codes (QVIT_ENULL); layout (QVIT_EINVAL); the geometry, by the
+ * rules of qvit_im2col_quant_i8 (QVIT_EINVAL); C > 16 (QVIT_EINVAL); kpad < C*kh*kw, kpad % 16, ldc < kpad
+ * (QVIT_EINVAL); ldc % 16 or codes off 16 bytes (QVIT_EALIGN); B == 0 returns QVIT_OK without a launch.
+ */
+int qvit_im2col_u8_i8(const uint8_t* img, int64_t B, int64_t C, int64_t H, int64_t W, int layout,
+                      int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
+                      const int8_t* code_table, int8_t* codes, int64_t ldc, int64_t kpad, hipStream_t stream);
+
+/*
+ * out[b][c][y][x] = value_table[c][img(b, c, y, x)]: the normalised fp32 NCHW image of a uint8 one, for the routes
+ * that read fp32 (transforms.ToTensor + transforms.Normalize, predict.py:18-19, as a lookup).
+ *   img         : as above, either layout, any alignment
+ *   value_table : fp32 [C][256], C <= 16 (held in LDS)
+ *   out         : fp32 [B][C][H][W] contiguous
+ * Checks, in this order: a NULL pointer (QVIT_ENULL); layout, B < 0, C, H or W < 1, B, H or W > 2^20, C > 16
+ * (QVIT_EINVAL); value_table or out off 4 bytes (QVIT_EALIGN); B == 0 returns QVIT_OK without a launch.
+ */
+int qvit_u8_normalize_f32(const uint8_t* img, int64_t B, int64_t C, int64_t H, int64_t W, int layout,
+                          const float* value_table, float* out, hipStream_t stream);
 
 /*
  * LayerNorm (biased variance, eps) followed by the next layer's activation quantizer.

@@ -46,6 +46,10 @@ ULTRA_F32 = 2
 
 EPI_TABLE_MAX_NB = 3800
 
+U8_NCHW = 0
+U8_NHWC = 1
+U8_MAX_C = 16   # channels whose [C][256] tables the uint8 kernels hold in LDS
+
 TILE_N = 256
 TILE_K = 128
 
@@ -71,6 +75,9 @@ _SIGNATURES = {
     "qvit_pack_weight_w8r": [_c_p, _i64, _i64, _c_p, _c_p],
     "qvit_im2col_quant_i8": [_c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                              _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i64, _c_p],
+    "qvit_im2col_u8_i8": [_c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                          _c_p, _c_p, _i64, _i64, _c_p],
+    "qvit_u8_normalize_f32": [_c_p, _i64, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p],
     "qvit_layernorm_quant_i8": [_c_p, _i64, _i64, _i64, _c_p, _c_p, _f32, _i32, _c_p, _c_p, _c_p, _i32,
                                 _c_p, _i64, _i64, _c_p, _c_p],
     "qvit_gemm": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i32, _c_p, _i64,
@@ -449,6 +456,43 @@ def im2col_quant_i8(x: torch.Tensor, kh: int, kw: int, sh: int, sw: int, ph: int
     _check(load().qvit_im2col_quant_i8(_ptr(x), B, C, H, W, kh, kw, sh, sw, ph, pw, dh, dw, qtype, _ptr(d),
                                        _ptr(qm), _ptr(t), levels, _ptr(out), out.stride(0), kpad,
                                        _stream(x.device)), "qvit_im2col_quant_i8")
+    return out
+
+
+def u8_image_layout(img: torch.Tensor) -> Tuple[torch.Tensor, int]:
+    """(tensor, layout) the uint8 kernels read for a [B, C, H, W] uint8 image: a contiguous tensor as it is (NCHW), a
+    channels_last one in place (NHWC: a decoder's [B, H, W, C] output seen through permute), anything else after
+    one contiguous copy."""
+    assert img.dtype == torch.uint8 and img.dim() == 4
+    if img.is_contiguous():
+        return img, U8_NCHW
+    if img.is_contiguous(memory_format=torch.channels_last):
+        return img, U8_NHWC
+    return img.contiguous(), U8_NCHW
+
+
+def im2col_u8_i8(img: torch.Tensor, kh: int, kw: int, sh: int, sw: int, ph: int, pw: int, dh: int, dw: int,
+                 code_table: torch.Tensor, out: torch.Tensor, kpad: int) -> torch.Tensor:
+    """im2col codes of a uint8 [B, C, H, W] image through the int8 [C, 256] code table (qvit_im2col_u8_i8)."""
+    _require_gpu(img, "input")
+    img, layout = u8_image_layout(img)
+    B, C, H, W = img.shape
+    assert code_table.dtype == torch.int8 and code_table.is_contiguous() and tuple(code_table.shape) == (C, 256)
+    _check(load().qvit_im2col_u8_i8(_ptr(img), B, C, H, W, layout, kh, kw, sh, sw, ph, pw, dh, dw, _ptr(code_table),
+                                    _ptr(out), out.stride(0), kpad, _stream(img.device)), "qvit_im2col_u8_i8")
+    return out
+
+
+def u8_normalize_f32(img: torch.Tensor, value_table: torch.Tensor) -> torch.Tensor:
+    """value_table[c][img[b, c, y, x]] as a contiguous fp32 NCHW tensor (qvit_u8_normalize_f32)."""
+    _require_gpu(img, "input")
+    img, layout = u8_image_layout(img)
+    B, C, H, W = img.shape
+    assert value_table.dtype == torch.float32 and value_table.is_contiguous() and \
+        tuple(value_table.shape) == (C, 256)
+    out = torch.empty((B, C, H, W), dtype=torch.float32, device=img.device)
+    _check(load().qvit_u8_normalize_f32(_ptr(img), B, C, H, W, layout, _ptr(value_table), _ptr(out),
+                                        _stream(img.device)), "qvit_u8_normalize_f32")
     return out
 
 

@@ -1144,6 +1144,7 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
         nn.Conv2d.__init__(self, in_channels, out_channels, kernel_size, stride, padding, dilation, groups,
                            bias=bias)
         self.init_quantization(d_quant_init, t_quant_init, q_m_init, quant_type, quant_mode)
+        self._u8_input = None   # (mean, std) of set_uint8_input
 
     @staticmethod
     def from_module(module=None, d_quant_init=1.0, t_quant_init=1.0, q_m_init=1.0,
@@ -1165,11 +1166,65 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
     def _int_conv_ok(self) -> bool:
         return (self.groups == 1 and self.padding_mode == "zeros" and not isinstance(self.padding, str))
 
+    # -- uint8 image input: ToTensor + Normalize (predict.py:18-19) and quantize_act as tables of 256 entries --------
+    def set_uint8_input(self, mean, std) -> None:
+        """From now on a torch.uint8 input [B, C, H, W] (contiguous, or channels_last: a decoder's [B, H, W, C]
+        seen through permute) stands for the fp32 image (input / 255 - mean_c) / std_c, torchvision's ToTensor then
+        Normalize, every step rounded to fp32. `mean` and `std` are a scalar or one value per input channel. The
+        result equals forward() on that fp32 image bit for bit; a float input is taken as already normalised. The
+        setting is a plain attribute: it is not part of state_dict()."""
+        C = self.in_channels
+        if C > _lib.U8_MAX_C:
+            raise ValueError(f"uint8 input takes at most {_lib.U8_MAX_C} input channels, this layer has {C}")
+
+        def per_channel(v, name):
+            vals = torch.as_tensor(v, dtype=torch.float64).detach().cpu().reshape(-1)
+            if vals.numel() == 1 and not isinstance(v, (tuple, list)):
+                vals = vals.expand(C)
+            if vals.numel() != C:
+                raise ValueError(f"{name}: {vals.numel()} values for {C} input channels")
+            vals = vals.to(torch.float32)   # as the table will hold them
+            if not bool(torch.isfinite(vals).all()):
+                raise ValueError(f"{name} must be finite, got {v!r}")
+            return tuple(vals.tolist())
+
+        mean, std = per_channel(mean, "mean"), per_channel(std, "std")
+        if any(s == 0.0 for s in std):
+            raise ValueError(f"std must not be zero, got {std!r}")
+        self._u8_input = (mean, std)
+
+    def clear_uint8_input(self) -> None:
+        self._u8_input = None
+
+    @property
+    def uint8_input(self):
+        """(mean, std), each a tuple of in_channels floats, or None."""
+        return getattr(self, "_u8_input", None)
+
+    def _u8_tables(self, plan: QuantPlan):
+        """(V, T) on the device for the current setting, kept with the plan: V fp32 [C, 256], the normalised value
+        of every byte; T int8 [C, 256] = the layer's activation codes of V through qvit_quantize_act_i8, the
+        quant_code every other producer of codes runs (None off the integer path)."""
+        key = self.uint8_input
+        cached = plan.extra.get("u8_tables")
+        if cached is not None and cached[0] == key:
+            return cached[1], cached[2]
+        mean, std = (torch.tensor(v, dtype=torch.float32) for v in key)
+        V = ((torch.arange(256, dtype=torch.float32).div(255)[None, :] - mean[:, None]) / std[:, None]) \
+            .contiguous().to(plan.device)
+        T = None
+        if plan.int_path:
+            T = torch.empty((V.shape[0], 256), dtype=torch.int8, device=plan.device)
+            _lib.quantize_act_i8(V, plan.qtype, plan.d_act, plan.qm_act, plan.t_act, 0, T, 256)
+        plan.extra["u8_tables"] = (key, V, T)
+        return V, T
+
     def conv_codes_gemm(self, input_: torch.Tensor, epilogue: int = _lib.EPI_F32):
         """im2col + quantize + contraction. Returns ([B*OH*OW, Cout] NHWC rows, (B, OH, OW))."""
         plan = self.quant_plan()
         x = input_.detach()
-        if x.dtype != torch.float32 or not x.is_contiguous():
+        u8 = x.dtype == torch.uint8 and self.uint8_input is not None
+        if not u8 and (x.dtype != torch.float32 or not x.is_contiguous()):
             x = x.float().contiguous()
         B, C, H, W = x.shape
         kh, kw = self.kernel_size
@@ -1178,8 +1233,11 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
         dh, dw = self.dilation
         OH, OW = _lib.conv_out_hw(H, W, self.kernel_size, self.stride, self.padding, self.dilation)
         codes = torch.empty((B * OH * OW, plan.kpad), dtype=torch.int8, device=x.device)
-        _lib.im2col_quant_i8(x, kh, kw, sh, sw, ph, pw, dh, dw, plan.qtype, plan.d_act, plan.qm_act, plan.t_act, 0,
-                             codes, plan.kpad)
+        if u8:
+            _lib.im2col_u8_i8(x, kh, kw, sh, sw, ph, pw, dh, dw, self._u8_tables(plan)[1], codes, plan.kpad)
+        else:
+            _lib.im2col_quant_i8(x, kh, kw, sh, sw, ph, pw, dh, dw, plan.qtype, plan.d_act, plan.qm_act, plan.t_act,
+                                 0, codes, plan.kpad)
         trace_codes(self, codes, plan.k)
         out = self.gemm_codes(codes, plan, epilogue)
         return out, (B, OH, OW)
@@ -1187,7 +1245,12 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
     def forward(self, input_: torch.Tensor) -> torch.Tensor:
         self._check_input(input_)
         plan = self.quant_plan()
-        if self._records_grad(input_):
+        live = self._records_grad(input_)
+        if input_.dtype == torch.uint8 and self.uint8_input is not None and \
+                (live or not (plan.int_path and self._int_conv_ok())):
+            # every route but the integer path reads fp32 (and the autograd node saves it): the normalised image
+            input_ = _lib.u8_normalize_f32(input_, self._u8_tables(plan)[0])
+        if live:
             return self._forward_autograd(input_, plan)
         return self._forward_plan(input_, plan)
 

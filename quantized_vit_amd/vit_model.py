@@ -589,6 +589,16 @@ class VisionTransformer(nn.Module):
         nn.init.trunc_normal_(self.cls_token, std=0.02)
         self.apply(_init_vit_weights)
 
+    def set_uint8_input(self, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5)) -> None:
+        """Lets forward() take the image as torch.uint8 [B, C, H, W] (contiguous or channels_last): the patch
+        embedding then applies ToTensor + Normalize(mean, std) itself (QuantizeConv2d.set_uint8_input; the defaults
+        are predict.py:19's). Needs the quantized model: the patch embedding must be a QuantizeConv2d."""
+        proj = getattr(self.patch_embed, "proj", None)
+        if not isinstance(proj, QuantizeConv2d):
+            raise TypeError(f"set_uint8_input: patch_embed.proj is {type(proj).__name__}, not a QuantizeConv2d "
+                            "(swap the model's layers with model_to_quantize_model first)")
+        proj.set_uint8_input(mean, std)
+
     def forward_features(self, x):
         x = self.patch_embed(x)
         live = torch.is_grad_enabled() and (x.requires_grad or any(
