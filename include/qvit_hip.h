@@ -15,6 +15,9 @@
  *                             (SymQuantizerLinear.backward) and :248-290 (DGEQuantizer.backward): grad_x and the
  *                             three quantizer-scalar gradients in one streaming pass with a deterministic
  *                             two-stage reduction (the reference: ~30 elementwise launches and three host syncs).
+ *   qvit_quant_error          the squared error of those quantizers' forward (quant_layers.py:41-69, :137-161) against
+ *                             their un-rounded input, for up to 64 candidate (d_quant, q_m) pairs in one pass: the
+ *                             scoring step of a clip search that stands in for GETA's learned parameters.
  *   qvit_pack_weight          quant_layers.py:332-354 (QuantizeMixin.quantize_weight) + the GEMM operand
  *                             layout: codes packed int4 (8 per u32) or int8, rows padded/permuted.
  *   qvit_im2col_quant_i8      quant_layers.py:575-587 (QuantizeConv2d.forward): the conv input patches
@@ -179,6 +182,41 @@ int qvit_quant_backward(const float* x, const float* grad_out, int64_t n, int qt
                         float clip_lo, float clip_hi, float dge_k,
                         float* grad_x, float* grad_scalars /* [3] */,
                         void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/*
+ * Quantization error of x under ncand candidate quantizers that share the type and t: the scoring pass of an
+ * error-minimising clip search (calibrate.py; GETA's projection picks d = q_m^t / (2^(b-1) - 1) from the same
+ * family, optimizer/geta.py:788-804). One read of x per block of 16 candidates replaces one qvit_fake_quant_f32
+ * pass and one reduction per candidate.
+ *   x        : fp32 [rows][ldx], cols <= ldx; columns >= cols are never read. May be NULL when rows * cols == 0.
+ *   d, q_m   : device float[ncand], 1 <= ncand <= 64. t: device float[1] shared by all candidates (NULL for
+ *              QVIT_QT_LINEAR). qtype is QVIT_QT_LINEAR or QVIT_QT_NONLINEAR; QVIT_QT_FORCE_CAREFUL-style flag bits
+ *              are accepted and change nothing (every element takes the careful sequence here).
+ *   err[c]   : double, sum over the elements of ((double)p - (double)fq)^2 with fq = the fp32 value
+ *              qvit_fake_quant_f32 returns for x under (d[c], q_m[c], t), rounding ties included, and the target
+ *              p = x (linear) or sgn(x) exp(t log|x|) (nonlinear: the un-rounded fp32 input_pow of
+ *              quant_layers.py:63, taken once per element; sgn is torch.sign, 0 at 0).
+ *   nclip[c] : int64, the number of elements with |x| >= q_m[c] (the saturation mask, :67, :159).
+ *   accumulate : 0 overwrites err and nclip; otherwise the call adds to what they hold, so a caller streams batches.
+ *   workspace  : qvit_quant_error_workspace_bytes(rows, cols, ncand) bytes (16 per workgroup and candidate, at most
+ *              1024 workgroups), 8-byte aligned, contents irrelevant.
+ * rows * cols == 0 writes zeros, or nothing under accumulate. A NaN or infinite x makes every err[c] non-finite (it
+ * is not masked) and is counted in nclip only where |x| >= q_m[c] holds (never for a NaN).
+ * Reduction: per-thread double accumulation, a fixed-order wave / workgroup tree, one partial per workgroup and
+ * candidate, folded in index order by a second launch that also applies `accumulate`. No atomics: two identical
+ * calls give identical bits. A thread takes 4 consecutive elements per step as one 16-byte load when x is 16-byte
+ * aligned and cols % 4 == 0, ldx % 4 == 0, else one by one with the same element-to-thread map: the same bits.
+ * 32-bit indexing when rows * ldx < 2^31 - 2^21, else 64-bit (the rule of qvit_im2col_quant_i8).
+ * Order of the checks (part of the ABI): d, q_m, err, nclip or workspace NULL (QVIT_ENULL); the qtype (unknown
+ * enum, stray flag bits, QVIT_QT_ULTRA_ACT: QVIT_EINVAL); nonlinear with t NULL (QVIT_ENULL); the sizes (ncand
+ * outside 1 .. 64, rows < 0, cols < 0, ldx < cols, rows * ldx > 2^48: QVIT_EINVAL); a short workspace
+ * (QVIT_EINVAL); x NULL with rows * cols > 0 (QVIT_ENULL); alignment (x, d, q_m, t 4 bytes; err, nclip, workspace
+ * 8: QVIT_EALIGN). qvit_quant_error_workspace_bytes returns QVIT_EINVAL on the same size errors (with ldx = cols).
+ */
+int64_t qvit_quant_error_workspace_bytes(int64_t rows, int64_t cols, int ncand);
+int qvit_quant_error(const float* x, int64_t rows, int64_t cols, int64_t ldx, int qtype, const float* d,
+                     const float* q_m, const float* t, int ncand, int accumulate, double* err, int64_t* nclip,
+                     void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 /*
  * y = GELU(x) elementwise over n contiguous floats: nn.GELU() (QViT_with_GETA/vit_model.py:173,242), bit-identical

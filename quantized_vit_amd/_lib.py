@@ -64,6 +64,7 @@ _SIGNATURES = {
     "qvit_quantize_act_i8": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i64, _c_p],
     "qvit_fake_quant_f32": [_c_p, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
     "qvit_quant_backward": [_c_p, _c_p, _i64, _i32, _c_p, _c_p, _c_p, _f32, _f32, _f32, _c_p, _c_p, _c_p, _i64, _c_p],
+    "qvit_quant_error": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _i32, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_gelu_f32": [_c_p, _i64, _c_p, _c_p],
     "qvit_layernorm_quant_backward": [_c_p, _i64, _i64, _i64, _c_p, _c_p, _f32, _i32, _c_p, _c_p, _c_p, _f32, _f32,
                                       _c_p, _i64, _c_p, _i64, _c_p, _c_p, _c_p, _c_p, _i64, _c_p],
@@ -138,6 +139,7 @@ _SIGNATURES = {
 # name -> argtypes of the entry points returning int64_t
 INT64_FUNCS = {
     "qvit_quant_backward_workspace_bytes": [_i64],
+    "qvit_quant_error_workspace_bytes": [_i64, _i64, _i32],
     "qvit_layernorm_quant_backward_workspace_bytes": [_i64, _i64],
     "qvit_gelu_quant_backward_workspace_bytes": [_i64],
     "qvit_attention_backward_workspace_bytes": [_i64, _i64, _i64],
@@ -282,6 +284,43 @@ def quant_backward(x: torch.Tensor, grad_out: torch.Tensor, qtype: int, d: torch
                                    float(clip_hi), float(dge_k), _ptr(grad_x), _ptr(scalars), _ptr(ws), nbytes,
                                    _stream(xc.device)), "qvit_quant_backward")
     return grad_x, scalars
+
+
+QUANT_ERROR_MAX_CAND = 64
+
+
+def quant_error(x2d: torch.Tensor, qtype: int, d: torch.Tensor, q_m: torch.Tensor, t: Optional[torch.Tensor],
+                err: Optional[torch.Tensor] = None, nclip: Optional[torch.Tensor] = None, accumulate: bool = False):
+    """Squared quantization error and clip count of x2d (fp32 [rows, cols], unit column stride, any row stride) under
+    the candidates (d[c], q_m[c]) at one t (qvit_quant_error). Returns (err float64 [ncand], nclip int64 [ncand]) on
+    the device, no host sync; given buffers are written, or added to under `accumulate`."""
+    _require_gpu(x2d, "input")
+    if x2d.dtype != torch.float32 or x2d.dim() != 2 or (x2d.shape[1] > 1 and x2d.stride(1) != 1):
+        raise QvitError(f"quant_error: the input must be a float32 matrix with unit column stride (got {x2d.dtype}, "
+                        f"shape {tuple(x2d.shape)}, strides {tuple(x2d.stride())})")
+    dev = x2d.device
+    ncand = d.numel()
+    for name, v in (("d", d), ("q_m", q_m)):
+        if not (v.is_cuda and v.dtype == torch.float32 and v.dim() == 1 and v.is_contiguous() and v.numel() == ncand):
+            raise QvitError(f"quant_error: {name} must be a contiguous float32 device vector of {ncand} candidates")
+    if accumulate and (err is None or nclip is None):
+        raise QvitError("quant_error: accumulate needs the err and nclip buffers to add to")
+    if err is None:
+        err = torch.empty(ncand, dtype=torch.float64, device=dev)
+    if nclip is None:
+        nclip = torch.empty(ncand, dtype=torch.int64, device=dev)
+    for name, v, dt in (("err", err, torch.float64), ("nclip", nclip, torch.int64)):
+        if not (v.is_cuda and v.dtype == dt and v.is_contiguous() and v.numel() == ncand):
+            raise QvitError(f"quant_error: {name} must be a contiguous {dt} device vector of {ncand} elements")
+    rows, cols = x2d.shape
+    ldx = x2d.stride(0) if rows > 1 else max(cols, x2d.stride(0))
+    lib = load()
+    ws = _workspace(int(lib.qvit_quant_error_workspace_bytes(rows, cols, ncand)), "qvit_quant_error_workspace_bytes",
+                    None, dev)
+    _check(lib.qvit_quant_error(_ptr(x2d) if x2d.numel() else None, rows, cols, ldx, qtype, _ptr(d), _ptr(q_m), _ptr(t),
+                                ncand, int(bool(accumulate)), _ptr(err), _ptr(nclip), _ptr(ws),
+                                ws.numel() * ws.element_size(), _stream(dev)), "qvit_quant_error")
+    return err, nclip
 
 
 def gelu_f32(x: torch.Tensor) -> torch.Tensor:

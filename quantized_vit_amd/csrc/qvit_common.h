@@ -114,6 +114,17 @@ QVIT_DEV float quant_code(float x, const QParams& p) {
   return need ? quant_fixup(x, p) : k;
 }
 
+// quant_code for a caller that already holds the careful power pw = p(|x|) (|x| for the linear type,
+// exp_cr(t * log_cr(|x|)) for the nonlinear one) and scores x against many (d, q_m, L) at one t: the careful
+// sequence with the saturation, sign and zero masks of quant_fast. The fast path only ever stands in for this
+// sequence, so the code is quant_code's for every x, rounding ties and NaN (0) included. Reads p.d, p.qm, p.L.
+QVIT_DEV float quant_code_from_pow(float x, float pw, const QParams& p) {
+  const float a = fabsf(x);
+  float k = (a >= p.qm) ? p.L : rintf(pw / p.d);
+  k = copysignf(k, x);
+  return (a > 0.f) ? k : 0.f;
+}
+
 // The reference's fp32 fake-quant value for the same element (d * k, rounded once in fp32,
 // then the sign applied) — used by qvit_fake_quant_f32.
 QVIT_DEV float fake_quant_value(float x, const QParams& p) {
