@@ -18,6 +18,10 @@
  *   qvit_quant_error          the squared error of those quantizers' forward (quant_layers.py:41-69, :137-161) against
  *                             their un-rounded input, for up to 64 candidate (d_quant, q_m) pairs in one pass: the
  *                             scoring step of a clip search that stands in for GETA's learned parameters.
+ *   qvit_qat_step / qvit_qat_quant_step
+ *                             OTO/optimizer/geta.py:571-804, :873-943 and base_optimizer.py:40-86: the warm-up, bit-range
+ *                             projection and fix stages of the GETA optimizer as one multi-tensor launch for the dense
+ *                             tensors and one for the quantizer scalars, with no .item() on the way.
  *   qvit_pack_weight          quant_layers.py:332-354 (QuantizeMixin.quantize_weight) + the GEMM operand
  *                             layout: codes packed int4 (8 per u32) or int8, rows padded/permuted.
  *   qvit_im2col_quant_i8      quant_layers.py:575-587 (QuantizeConv2d.forward): the conv input patches
@@ -217,6 +221,71 @@ int64_t qvit_quant_error_workspace_bytes(int64_t rows, int64_t cols, int ncand);
 int qvit_quant_error(const float* x, int64_t rows, int64_t cols, int64_t ldx, int qtype, const float* d,
                      const float* q_m, const float* t, int ncand, int accumulate, double* err, int64_t* nclip,
                      void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/*
+ * The quantization-aware stages of the GETA optimizer (optimizer/geta.py:571-804, :873-943 with the pruning stages
+ * absent; grad_variant of optimizer/base_optimizer.py:40-86) as at most two launches per step, neither of which
+ * reads anything back to the host. fp32, one IEEE operation per reference operation in the reference's order, fmaf
+ * where torch's CPU add_(b, alpha=s) is a fused multiply-add, correctly rounded division and sqrt, safe_guard 1e-8
+ * added after the sqrt.
+ *
+ * Hyper-parameters, by value, the same for both entry points:
+ *   variant        : QVIT_QAT_SGD (momentum, dampening, coupled weight decay), QVIT_QAT_ADAM, QVIT_QAT_ADAMW (decay
+ *                    applied to p at the step's rate before the gradient step).
+ *   first_step     : non-zero on the optimizer's first step: every moment becomes grad (grad^2), un-scaled
+ *                    (base_optimizer.py:20-21, :31-32); a descriptor's own flag says the same for one tensor.
+ *   lr, lr_quant   : the rates of learning-rate class 0 and 1.
+ *   first_momentum, second_momentum : the moment decay factors; <= 0 keeps no such moment (the gradient stands in).
+ *   alpha1, alpha2 : 1 - dampening of the two moment updates as the host rounds them from double (adam: 1 - the
+ *                    momenta; sgd: alpha1 = 1 - dampening, alpha2 unused).
+ *   weight_decay   : 0 for none.  bias_correction1/2: 1 - momentum^step (adam, adamw).
+ *   clip_lo, clip_hi : grad is clamped into [clip_lo, clip_hi] as it is loaded (geta.py:160-165; -inf, +inf: off).
+ *
+ * qvit_qat_step — every dense tensor from one launch.
+ *   tensors : device table of ntensors descriptors of 48 bytes: { float* p; const float* grad; float* m; float* v;
+ *             int64_t numel; int32_t lr_class; int32_t flags; }. grad NULL skips the tensor and leaves its moments
+ *             untouched (base_optimizer.py:51); m / v NULL where the variant keeps no such moment; flags bit 0: this
+ *             tensor's first step. The tensors stay in their own storage.
+ *   chunks  : device list of nchunks pairs { int32_t tensor; int32_t index; }: elements [4096 index, 4096 (index +
+ *             1)) of that tensor, clipped to numel. Workgroups (at most 1024) stride over the list. Pairs that name
+ *             no tensor or start past numel are skipped. A tensor whose p, grad, m and v are all 16-byte aligned is
+ *             read and written 16 bytes at a time with a scalar tail; any other one element at a time: same bits.
+ * Order of the checks (part of the ABI): tensors or chunks NULL (QVIT_ENULL); either off 8 bytes (QVIT_EALIGN);
+ * ntensors < 0, nchunks < 0 or nchunks > 2^40 (QVIT_EINVAL); unknown variant (QVIT_EINVAL). ntensors == 0 or
+ * nchunks == 0 is a no-op success.
+ *
+ * qvit_qat_quant_step — every quantizer scalar and the stage's projection, one thread per (layer, side).
+ *   quants  : device table of nquants descriptors of 64 bytes: { float* s[3]; const float* g[3]; float* mom;
+ *             int32_t side; int32_t flags; }: d_quant, q_m, t_quant (t NULL: t = 1, the linear type), their gradients
+ *             (NULL: that scalar is skipped), six floats of moments (first of d, q_m, t, then second), side 0 weight /
+ *             1 activation, flags bits 0..2: first step of d, q_m, t.
+ *   Update  : all three at lr_quant. In QVIT_QAT_RANGE an activation-side triple is first stepped at lr and then
+ *             again at lr_quant from the same grad_variant, as geta.py:598-630 followed by :667-697 does.
+ *   stage   : QVIT_QAT_WARMUP no projection; QVIT_QAT_RANGE d is clamped into [d(max_bit), d(min_bit)] of its side
+ *             with d(b) = exp(t log(max(|q_m|, 1e-10))) / (2^(b-1) - 1) evaluated in double from the updated q_m
+ *             and t and rounded to fp32 (geta.py:787-804); QVIT_QAT_FIX d = d(bits[i]). With first_fix non-zero
+ *             bits[i] = rint(log2(exp(t log|q_m|) / |d| + 1) + 1) (half to even; geta.py:774-785) is taken first,
+ *             from the scalars as the step finds them (the reference reads them before its update, :932-940).
+ *   bits    : device int32[nquants], written under first_fix, read in QVIT_QAT_FIX.
+ * Order of the checks: quants or bits NULL (QVIT_ENULL); quants off 8 bytes or bits off 4 (QVIT_EALIGN);
+ * nquants < 0 (QVIT_EINVAL); unknown variant (QVIT_EINVAL); unknown stage (QVIT_EINVAL); a bit range outside
+ * 2 <= min <= max <= 32 on either side (QVIT_EINVAL). nquants == 0 is a no-op success.
+ */
+#define QVIT_QAT_SGD    0
+#define QVIT_QAT_ADAM   1
+#define QVIT_QAT_ADAMW  2
+#define QVIT_QAT_WARMUP 0
+#define QVIT_QAT_RANGE  1
+#define QVIT_QAT_FIX    2
+int qvit_qat_step(const void* tensors, int ntensors, const void* chunks, int64_t nchunks, int variant,
+                  int first_step, float lr, float lr_quant, float first_momentum, float second_momentum,
+                  float alpha1, float alpha2, float weight_decay, float bias_correction1, float bias_correction2,
+                  float clip_lo, float clip_hi, hipStream_t stream);
+int qvit_qat_quant_step(const void* quants, int nquants, int32_t* bits, int stage, int first_fix, int variant,
+                        int first_step, float lr, float lr_quant, float first_momentum, float second_momentum,
+                        float alpha1, float alpha2, float weight_decay, float bias_correction1,
+                        float bias_correction2, float clip_lo, float clip_hi, int min_bit_wt, int max_bit_wt,
+                        int min_bit_act, int max_bit_act, hipStream_t stream);
 
 /*
  * y = GELU(x) elementwise over n contiguous floats: nn.GELU() (QViT_with_GETA/vit_model.py:173,242), bit-identical

@@ -46,6 +46,12 @@ ULTRA_F32 = 2
 
 EPI_TABLE_MAX_NB = 3800
 
+QAT_SGD, QAT_ADAM, QAT_ADAMW = 0, 1, 2
+QAT_WARMUP, QAT_RANGE, QAT_FIX = 0, 1, 2
+QAT_CHUNK = 4096          # elements of one chunk of qvit_qat_step
+QAT_TENSOR_BYTES = 48     # its tensor descriptor, and the (layer, side) descriptor of qvit_qat_quant_step
+QAT_QUANT_BYTES = 64
+
 U8_NCHW = 0
 U8_NHWC = 1
 U8_MAX_C = 16   # channels whose [C][256] tables the uint8 kernels hold in LDS
@@ -65,6 +71,8 @@ _SIGNATURES = {
     "qvit_fake_quant_f32": [_c_p, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
     "qvit_quant_backward": [_c_p, _c_p, _i64, _i32, _c_p, _c_p, _c_p, _f32, _f32, _f32, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_quant_error": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _i32, _c_p, _c_p, _c_p, _i64, _c_p],
+    "qvit_qat_step": [_c_p, _i32, _c_p, _i64, _i32, _i32] + [_f32] * 11 + [_c_p],
+    "qvit_qat_quant_step": [_c_p, _i32, _c_p, _i32, _i32, _i32, _i32] + [_f32] * 11 + [_i32] * 4 + [_c_p],
     "qvit_gelu_f32": [_c_p, _i64, _c_p, _c_p],
     "qvit_layernorm_quant_backward": [_c_p, _i64, _i64, _i64, _c_p, _c_p, _f32, _i32, _c_p, _c_p, _c_p, _f32, _f32,
                                       _c_p, _i64, _c_p, _i64, _c_p, _c_p, _c_p, _c_p, _i64, _c_p],
@@ -321,6 +329,26 @@ def quant_error(x2d: torch.Tensor, qtype: int, d: torch.Tensor, q_m: torch.Tenso
                                 ncand, int(bool(accumulate)), _ptr(err), _ptr(nclip), _ptr(ws),
                                 ws.numel() * ws.element_size(), _stream(dev)), "qvit_quant_error")
     return err, nclip
+
+
+def qat_step(tensors: torch.Tensor, ntensors: int, chunks: torch.Tensor, nchunks: int, hyper: tuple) -> None:
+    """One dense optimizer step over the device descriptor table (qvit_qat_step). `hyper`: (variant, first_step, lr,
+    lr_quant, first_momentum, second_momentum, alpha1, alpha2, weight_decay, bias_correction1, bias_correction2,
+    clip_lo, clip_hi) as include/qvit_hip.h lists them."""
+    _require_gpu(tensors, "tensor table")
+    _require_gpu(chunks, "chunk list")
+    _check(load().qvit_qat_step(_ptr(tensors), ntensors, _ptr(chunks), nchunks, *hyper, _stream(tensors.device)),
+           "qvit_qat_step")
+
+
+def qat_quant_step(quants: torch.Tensor, nquants: int, bits: torch.Tensor, stage: int, first_fix: bool, hyper: tuple,
+                   bit_ranges: tuple) -> None:
+    """The quantizer scalars' step and projection (qvit_qat_quant_step). `bit_ranges`: (min_bit_wt, max_bit_wt,
+    min_bit_act, max_bit_act)."""
+    _require_gpu(quants, "quantizer table")
+    assert bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and bits.numel() >= nquants
+    _check(load().qvit_qat_quant_step(_ptr(quants), nquants, _ptr(bits), stage, int(bool(first_fix)), *hyper,
+                                      *bit_ranges, _stream(quants.device)), "qvit_qat_quant_step")
 
 
 def gelu_f32(x: torch.Tensor) -> torch.Tensor:

@@ -27,7 +27,8 @@ patch rows plus qvit_col2im_quant_backward, see CONV_BACKWARD_GEMM; otherwise to
 reference's quantizer backwards (quant_layers.py:71-125, 163-205) as
 one fused HIP pass each (qvit_quant_backward): grad_x plus the gradients of d_quant, q_m and t_quant through
 a deterministic reduction. SymQuantizerLinear / SymQuantizerNonLinear / DGEQuantizer expose the same pass at
-the function level. Under torch.no_grad() nothing of this runs. The GETA optimizer is out of scope.
+the function level. Under torch.no_grad() nothing of this runs. The quantization stages of the GETA optimizer are qat_optim.py; its
+pruning stages are out of scope.
 """
 from __future__ import annotations
 
