@@ -22,6 +22,11 @@
  *                             OTO/optimizer/geta.py:571-804, :873-943 and base_optimizer.py:40-86: the warm-up, bit-range
  *                             projection and fix stages of the GETA optimizer as one multi-tensor launch for the dense
  *                             tensors and one for the quantizer scalars, with no .item() on the way.
+ *   qvit_prune_scores / qvit_prune_scores_finish / qvit_prune_joint_scalars / qvit_prune_joint_reduce /
+ *   qvit_prune_joint_finish / qvit_prune_joint_apply
+ *                             OTO/optimizer/geta.py:167-248, :281-521, :944-1026 and base_hybrid_sparse_optimizer.py:
+ *                             194-291: the saliency scores and the joint pruning and quantization stage for declared
+ *                             row groups, a fixed number of launches per step and no .item().
  *   qvit_pack_weight          quant_layers.py:332-354 (QuantizeMixin.quantize_weight) + the GEMM operand
  *                             layout: codes packed int4 (8 per u32) or int8, rows padded/permuted.
  *   qvit_im2col_quant_i8      quant_layers.py:575-587 (QuantizeConv2d.forward): the conv input patches
@@ -286,6 +291,83 @@ int qvit_qat_quant_step(const void* quants, int nquants, int32_t* bits, int stag
                         float alpha1, float alpha2, float weight_decay, float bias_correction1,
                         float bias_correction2, float clip_lo, float clip_hi, int min_bit_wt, int max_bit_wt,
                         int min_bit_act, int max_bit_act, hipStream_t stream);
+
+/*
+ * The pruning stages of the GETA optimizer for declared row groups (optimizer/geta.py:167-248, :281-521, :944-1026;
+ * base_hybrid_sparse_optimizer.py:194-291; the importance_score package). A group is a set of member tensors sliced along
+ * dim 0: row r of the group is row r of every member. The launches per step do not depend on the number of groups,
+ * and nothing is read back. The hyper-parameters are those of qvit_qat_step, and the gradient variant is recomputed
+ * in registers from grad, m and v by the function qvit_qat_step runs.
+ *
+ * Device tables (the host fills them as int64 rows):
+ *   groups  : ngroups descriptors of 64 bytes: { float* d; const float* q_m; const float* t; int32_t member_begin,
+ *             member_count; int32_t rows; int32_t joint; int32_t red_begin, red_count; int64_t elems; int64_t
+ *             reserved; }: the weight quantizer scalars of the group's layer (t NULL: the linear type), its members
+ *             [member_begin, member_begin + member_count) of `members`, its row count, joint = 1 while it has active
+ *             redundant rows, the range of its redundant rows in the reduce's item list, and elems = the elements of
+ *             one row over all members.
+ *   members : nmembers descriptors of 48 bytes: { float* p; const float* grad; float* m; float* v; int64_t width;
+ *             int32_t quantized; int32_t flags; }: qvit_qat_step's tensor descriptor with the row width in place of
+ *             numel; quantized = 1 for the layer's weight; flags bit 0: this tensor's first step. A member whose
+ *             four pointers are 16-byte aligned and whose width is a multiple of 4 moves 16 bytes at a time, any
+ *             other one element at a time: same bits.
+ *   items   : nitems entries of 16 bytes: { int32_t group, row, state, reserved; }, state 0 important, 1 active
+ *             redundant, 2 pruned. A wave owns one item. Items that name no group or no row of it are skipped.
+ *
+ * qvit_prune_scores: sums[3 i .. 3 i + 2] = sum p^2, sum g^2, sum p g of item i's row over the members, g the
+ *   gradient variant, in double (a member without grad adds to sum p^2 only).
+ * qvit_prune_scores_finish: scores[i] = sum_c w_c score_c(i) / (sqrt(1e-8 + sum_j score_c(j)^2) + 1e-8) over the
+ *   criteria magnitude = sqrt(sum p^2), avg_magnitude = magnitude / (elems + 1e-6), cosine = sum p g / (|p| + 1e-8) /
+ *   (|g| + 1e-8) + 1, taylor1 = |sum p g|, taylor2 = 0.5 taylor1^2, in that order; a weight of 0 leaves a criterion
+ *   out. One workgroup.
+ * qvit_prune_joint_scalars: quants as qvit_qat_quant_step's. A weight-side triple: q_m and t step at lr_quant
+ *   without decay, d only moves its moments (geta.py:952-960); an activation-side triple takes the range stage's
+ *   activation pass (:667-721): one step at lr_quant, then d clamped into [d(max_bit_act), d(min_bit_act)].
+ * qvit_prune_joint_reduce: items lists the active redundant rows, a group's rows contiguous at [red_begin, red_begin +
+ *   red_count); partials[6 i ..] = <clip, g>, |clip|^2, |g|^2, <res, g>, |res|^2, sum clip of that row, clip and res
+ *   by _clip_helper and _residual_helper (:821-850) for the quantized member, clip = p and res = 0 for the others.
+ * qvit_prune_joint_finish: one workgroup per group folds its partials in index order and evaluates compute_gamma_d
+ *   (:373-499) in double with every branch; writes d to the group's d_quant, gamma[g] and info[g] (bits 0..2: 0
+ *   mean(clip) < 1e-8, 1 non-finite cosine, 2 the schedule, 3 negative cosine, 4 / 5 clamped from above / below;
+ *   bit 3 d = d_quant_upper by the safeguard, bit 4 the x 0.8 loop ran, bit 5 the final min took d_quant_upper, bit 6
+ *   the loop was cut after 861 turns (fp32's whole exponent range): d = d_quant_upper, gamma = 0, where the reference
+ *   would not end; -1 for a group that is not joint). lr is the host's double; period and t_in_period give the
+ *   schedule 1 - (period - t - 1) / (period - t).
+ * qvit_prune_joint_apply: items lists every row of every group. Joint groups: on redundant rows p -= gamma *
+ *   quantize(p) (weight; _quantize_helper :806-819 with the new d) or gamma * p (others), then p -= lr g without
+ *   adamw's decay (:982-1008); other groups: the dense step. Moments as qvit_qat_step leaves them; pruned rows are
+ *   written as zeros (base_hybrid_sparse_optimizer.py:194-211).
+ * Order of the checks (part of the ABI), for scores, joint_reduce and joint_apply: a table or the output NULL
+ * (QVIT_ENULL); any of them off 8 bytes (QVIT_EALIGN); a count < 0 or nitems > 2^31 - 1 (QVIT_EINVAL); unknown variant
+ * (QVIT_EINVAL); a zero count is a no-op success. scores_finish: NULL; groups, items or sums off 8 bytes or scores
+ * off 4; counts. joint_scalars: NULL; off 8 bytes; nquants < 0; variant; the bit range. joint_finish: NULL; groups or
+ * partials off 8 bytes or gamma or info off 4; counts; period < 1 or t_in_period outside [0, period); the bit range.
+ */
+int qvit_prune_scores(const void* groups, int ngroups, const void* members, int nmembers, const void* items,
+                      int64_t nitems, double* sums, int variant, int first_step, float lr, float lr_quant,
+                      float first_momentum, float second_momentum, float alpha1, float alpha2, float weight_decay,
+                      float bias_correction1, float bias_correction2, float clip_lo, float clip_hi,
+                      hipStream_t stream);
+int qvit_prune_scores_finish(const void* groups, int ngroups, const void* items, int64_t nitems, const double* sums,
+                             double w_magnitude, double w_avg_magnitude, double w_cosine, double w_taylor1,
+                             double w_taylor2, float* scores, hipStream_t stream);
+int qvit_prune_joint_scalars(const void* quants, int nquants, int variant, int first_step, float lr, float lr_quant,
+                             float first_momentum, float second_momentum, float alpha1, float alpha2,
+                             float weight_decay, float bias_correction1, float bias_correction2, float clip_lo,
+                             float clip_hi, int min_bit_act, int max_bit_act, hipStream_t stream);
+int qvit_prune_joint_reduce(const void* groups, int ngroups, const void* members, int nmembers, const void* items,
+                            int64_t nitems, double* partials, int variant, int first_step, float lr, float lr_quant,
+                            float first_momentum, float second_momentum, float alpha1, float alpha2,
+                            float weight_decay, float bias_correction1, float bias_correction2, float clip_lo,
+                            float clip_hi, hipStream_t stream);
+int qvit_prune_joint_finish(const void* groups, int ngroups, const double* partials, int64_t npartials, double lr,
+                            int period, int t_in_period, int min_bit_wt, int max_bit_wt, float* gamma, int32_t* info,
+                            hipStream_t stream);
+int qvit_prune_joint_apply(const void* groups, int ngroups, const void* members, int nmembers, const void* items,
+                           int64_t nitems, const float* gamma, int variant, int first_step, float lr, float lr_quant,
+                           float first_momentum, float second_momentum, float alpha1, float alpha2,
+                           float weight_decay, float bias_correction1, float bias_correction2, float clip_lo,
+                           float clip_hi, hipStream_t stream);
 
 /*
  * y = GELU(x) elementwise over n contiguous floats: nn.GELU() (QViT_with_GETA/vit_model.py:173,242), bit-identical

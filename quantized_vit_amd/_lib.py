@@ -51,6 +51,10 @@ QAT_WARMUP, QAT_RANGE, QAT_FIX = 0, 1, 2
 QAT_CHUNK = 4096          # elements of one chunk of qvit_qat_step
 QAT_TENSOR_BYTES = 48     # its tensor descriptor, and the (layer, side) descriptor of qvit_qat_quant_step
 QAT_QUANT_BYTES = 64
+PRUNE_GROUP_BYTES = 64    # the group, member and item descriptors of the qvit_prune_* entry points
+PRUNE_MEMBER_BYTES = 48
+PRUNE_ITEM_BYTES = 16
+PRUNE_IMPORTANT, PRUNE_REDUNDANT, PRUNE_PRUNED = 0, 1, 2
 
 U8_NCHW = 0
 U8_NHWC = 1
@@ -73,6 +77,12 @@ _SIGNATURES = {
     "qvit_quant_error": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _i32, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_qat_step": [_c_p, _i32, _c_p, _i64, _i32, _i32] + [_f32] * 11 + [_c_p],
     "qvit_qat_quant_step": [_c_p, _i32, _c_p, _i32, _i32, _i32, _i32] + [_f32] * 11 + [_i32] * 4 + [_c_p],
+    "qvit_prune_scores": [_c_p, _i32, _c_p, _i32, _c_p, _i64, _c_p, _i32, _i32] + [_f32] * 11 + [_c_p],
+    "qvit_prune_scores_finish": [_c_p, _i32, _c_p, _i64, _c_p] + [_f64] * 5 + [_c_p, _c_p],
+    "qvit_prune_joint_scalars": [_c_p, _i32, _i32, _i32] + [_f32] * 11 + [_i32, _i32, _c_p],
+    "qvit_prune_joint_reduce": [_c_p, _i32, _c_p, _i32, _c_p, _i64, _c_p, _i32, _i32] + [_f32] * 11 + [_c_p],
+    "qvit_prune_joint_finish": [_c_p, _i32, _c_p, _i64, _f64, _i32, _i32, _i32, _i32, _c_p, _c_p, _c_p],
+    "qvit_prune_joint_apply": [_c_p, _i32, _c_p, _i32, _c_p, _i64, _c_p, _i32, _i32] + [_f32] * 11 + [_c_p],
     "qvit_gelu_f32": [_c_p, _i64, _c_p, _c_p],
     "qvit_layernorm_quant_backward": [_c_p, _i64, _i64, _i64, _c_p, _c_p, _f32, _i32, _c_p, _c_p, _c_p, _f32, _f32,
                                       _c_p, _i64, _c_p, _i64, _c_p, _c_p, _c_p, _c_p, _i64, _c_p],
@@ -349,6 +359,55 @@ def qat_quant_step(quants: torch.Tensor, nquants: int, bits: torch.Tensor, stage
     assert bits.is_cuda and bits.dtype == torch.int32 and bits.is_contiguous() and bits.numel() >= nquants
     _check(load().qvit_qat_quant_step(_ptr(quants), nquants, _ptr(bits), stage, int(bool(first_fix)), *hyper,
                                       *bit_ranges, _stream(quants.device)), "qvit_qat_quant_step")
+
+
+def prune_scores(groups: torch.Tensor, ngroups: int, members: torch.Tensor, nmembers: int, items: torch.Tensor,
+                 nitems: int, sums: torch.Tensor, weights: tuple, scores: torch.Tensor, hyper: tuple) -> None:
+    """The saliency score of every listed row (qvit_prune_scores, then qvit_prune_scores_finish). `weights`: the five
+    criteria weights in the header's order; `sums` float64 [nitems, 3] and `scores` float32 [nitems] are written."""
+    _require_gpu(groups, "group table")
+    assert sums.dtype == torch.float64 and sums.numel() >= 3 * nitems and scores.dtype == torch.float32 and \
+        scores.numel() >= nitems
+    lib, st = load(), _stream(groups.device)
+    _check(lib.qvit_prune_scores(_ptr(groups), ngroups, _ptr(members), nmembers, _ptr(items), nitems, _ptr(sums),
+                                 *hyper, st), "qvit_prune_scores")
+    _check(lib.qvit_prune_scores_finish(_ptr(groups), ngroups, _ptr(items), nitems, _ptr(sums),
+                                        *[float(w) for w in weights], _ptr(scores), st), "qvit_prune_scores_finish")
+
+
+def prune_joint_scalars(quants: torch.Tensor, nquants: int, hyper: tuple, min_bit_act: int, max_bit_act: int) -> None:
+    """The quantizer scalars of the joint groups' layers (qvit_prune_joint_scalars)."""
+    _require_gpu(quants, "quantizer table")
+    _check(load().qvit_prune_joint_scalars(_ptr(quants), nquants, *hyper, min_bit_act, max_bit_act,
+                                           _stream(quants.device)), "qvit_prune_joint_scalars")
+
+
+def prune_joint_reduce(groups: torch.Tensor, ngroups: int, members: torch.Tensor, nmembers: int, items: torch.Tensor,
+                       nitems: int, partials: torch.Tensor, hyper: tuple) -> None:
+    _require_gpu(groups, "group table")
+    assert partials.dtype == torch.float64 and partials.numel() >= 6 * nitems
+    _check(load().qvit_prune_joint_reduce(_ptr(groups), ngroups, _ptr(members), nmembers, _ptr(items), nitems,
+                                          _ptr(partials), *hyper, _stream(groups.device)), "qvit_prune_joint_reduce")
+
+
+def prune_joint_finish(groups: torch.Tensor, ngroups: int, partials: torch.Tensor, npartials: int, lr: float,
+                       period: int, t_in_period: int, min_bit_wt: int, max_bit_wt: int, gamma: torch.Tensor,
+                       info: torch.Tensor) -> None:
+    _require_gpu(groups, "group table")
+    assert partials.dtype == torch.float64 and partials.numel() >= 6 * npartials
+    assert gamma.dtype == torch.float32 and gamma.numel() >= ngroups and info.dtype == torch.int32 and \
+        info.numel() >= ngroups
+    _check(load().qvit_prune_joint_finish(_ptr(groups), ngroups, _ptr(partials), npartials, float(lr), period,
+                                          t_in_period, min_bit_wt, max_bit_wt, _ptr(gamma), _ptr(info),
+                                          _stream(groups.device)), "qvit_prune_joint_finish")
+
+
+def prune_joint_apply(groups: torch.Tensor, ngroups: int, members: torch.Tensor, nmembers: int, items: torch.Tensor,
+                      nitems: int, gamma: torch.Tensor, hyper: tuple) -> None:
+    _require_gpu(groups, "group table")
+    assert gamma.dtype == torch.float32 and gamma.numel() >= ngroups
+    _check(load().qvit_prune_joint_apply(_ptr(groups), ngroups, _ptr(members), nmembers, _ptr(items), nitems,
+                                         _ptr(gamma), *hyper, _stream(groups.device)), "qvit_prune_joint_apply")
 
 
 def gelu_f32(x: torch.Tensor) -> torch.Tensor:

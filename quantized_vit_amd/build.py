@@ -22,12 +22,12 @@ ARCH = "gfx950"
 SOURCES = ["quant_kernels.hip", "quant_backward.hip", "train_fuse.hip", "gemm_w4a8.hip", "gemm_ws.hip",
            "gemm_wonly.hip", "gemm_wgrad.hip", "attention.hip", "attention_backward.hip", "qkv_attention.hip",
            "ultra_conv.hip", "ultra_backward.hip", "ultra_bn_fuse.hip", "conv_backward.hip", "u8_input.hip",
-           "quant_error.hip", "qat_step.hip"]
+           "quant_error.hip", "qat_step.hip", "prune_step.hip"]
 # sources with inline-asm register loads: their device assembly is kept beside the objects (the very code in the
 # library) for tools/asm_load_check.py (tests/test_asm_loads.py)
 ASM_CHECKED = ["gemm_w4a8.hip", "ultra_conv.hip"]
 HEADERS = ["qvit_common.h", "attn_common.h", "attn32.h", "ln_common.h", "reduce_common.h", "quant_bwd_common.h",
-           "bf16x3.h", "ultra_quant_common.h", "diag_stamps.h"]
+           "bf16x3.h", "ultra_quant_common.h", "diag_stamps.h", "qat_common.h"]
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}",

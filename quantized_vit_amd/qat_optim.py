@@ -1,11 +1,14 @@
-"""QuantAwareOptimizer: the quantization-aware stages of the reference's GETA optimizer on the device.
+"""QuantAwareOptimizer: the reference's GETA optimizer on the device.
 
-OTO/optimizer/geta.py (GETA.step, :873-943) with the pruning stages absent, over OTO/optimizer/base_optimizer.py's
-grad_variant (:40-86): warm-up, bit-range projection with the reduction schedule, and the final "fix" stage. A step is
+OTO/optimizer/geta.py (GETA.step, :873-943) with the pruning stages absent unless row groups are declared, over
+OTO/optimizer/base_optimizer.py's grad_variant (:40-86): warm-up, bit-range projection with the reduction schedule,
+and the final "fix" stage. A step is
 two HIP launches (include/qvit_hip.h: qvit_qat_step for every dense tensor, qvit_qat_quant_step for every quantizer
 scalar and its projection) and no device-to-host copy: the reference makes a few torch launches per parameter and
 reads q_m and t_quant back with .item() per layer, side and step. The pruning stages (saliency scores, redundant
-groups, the joint stage) need the OTO graph tracer and its dependency groups and are out of scope.
+groups, the joint stage, geta.py:904-1026) run for row groups the user declares (PruneGroup; vit_mlp_prune_groups for
+the MLP hidden units of a ViT): the reference's optimizer takes ready-made parameter groups and only its graph tracer,
+which is out of scope, produces them. See the second half of this module.
 
 Reference behaviour kept as it is (the trained scalars are the product's input):
   * a tensor's first step makes its moment buffers grad and grad^2 themselves, not scaled by 1 - beta
@@ -92,8 +95,11 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
                  first_momentum: Optional[float] = None, second_momentum: Optional[float] = None,
                  dampening: Optional[float] = None, weight_decay: Optional[float] = None,
                  start_projection_step: int = 0, projection_steps: int = 1, projection_periods: int = 1,
-                 fix_after_step: int = 2, bit_reduction: int = 2, min_bit_wt: int = 4, max_bit_wt: int = 16,
-                 min_bit_act: int = 4, max_bit_act: int = 16, grad_clip: Optional[Tuple[float, float]] = None):
+                 fix_after_step: Optional[int] = None, bit_reduction: int = 2, min_bit_wt: int = 4,
+                 max_bit_wt: int = 16, min_bit_act: int = 4, max_bit_act: int = 16,
+                 grad_clip: Optional[Tuple[float, float]] = None, prune_groups: Optional[List["PruneGroup"]] = None,
+                 target_group_sparsity: float = 0.5, start_pruning_step: int = 1, pruning_steps: int = 1,
+                 pruning_periods: int = 1, group_divisible: int = 1, importance_score_criteria="default"):
         if variant not in _VARIANTS:
             raise ValueError(f"variant = {variant!r}: expected one of {sorted(_VARIANTS)}")
         for name, lo, hi in (("wt", min_bit_wt, max_bit_wt), ("act", min_bit_act, max_bit_act)):
@@ -102,13 +108,24 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
         adam = variant != "sgd"
         if adam and (first_momentum is None or second_momentum is None):
             raise ValueError(f"{variant} needs first_momentum and second_momentum")
+        if prune_groups is not None:
+            prune_groups = list(prune_groups)
+            _check_prune_groups(prune_groups)
         self.model = model
         self.variant = variant
         self.start_projection_step = int(start_projection_step)
         self.projection_steps = int(projection_steps)
         self.projection_periods = int(projection_periods)
         self.projection_period_duration = self.projection_steps // max(self.projection_periods, 1)
-        self.fix_after_step = int(fix_after_step)
+        if prune_groups is not None:
+            # the fix stage begins after the pruning steps (geta.py:931)
+            if fix_after_step is not None and int(fix_after_step) != int(start_pruning_step) + int(pruning_steps):
+                raise ValueError(f"fix_after_step = {fix_after_step} disagrees with start_pruning_step + pruning_steps "
+                                 f"= {int(start_pruning_step) + int(pruning_steps)}")
+            fix_after_step = int(start_pruning_step) + int(pruning_steps)
+        self.fix_after_step = 2 if fix_after_step is None else int(fix_after_step)
+        # the bit schedule runs while num_steps <= start_pruning_step (geta.py:885-902)
+        self._schedule_end = self.fix_after_step if prune_groups is None else int(start_pruning_step)
         self.bit_reduction = int(bit_reduction)
         self.min_bit_wt, self.max_bit_wt = int(min_bit_wt), int(max_bit_wt)
         self.min_bit_act, self.max_bit_act = int(min_bit_act), int(max_bit_act)
@@ -189,6 +206,17 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
             self._qrow[i, 7] = side
         self._ttable = _Upload(nd, self._trow.shape[1], self.device)
         self._qtable = _Upload(nq, self._qrow.shape[1], self.device)
+        self._prune: Optional[_PruneState] = None
+        if prune_groups is not None:
+            self._prune = _PruneState(self, prune_groups, float(target_group_sparsity), int(start_pruning_step),
+                                      int(pruning_steps), int(pruning_periods), int(group_divisible),
+                                      importance_score_criteria)
+            # the members leave the dense launch: qvit_prune_joint_apply steps them in every stage
+            keep = ~np.isin(chunks[:, 0], list(self._prune.member_dense)) if self._nchunks else np.zeros(0, bool)
+            chunks = chunks[keep]
+            self._nchunks = int(chunks.shape[0])
+            self._chunks = torch.from_numpy(np.ascontiguousarray(chunks if self._nchunks else
+                                                                 np.zeros((1, 2), np.int32))).to(self.device)
 
     # ---- the reference's small surface --------------------------------------------------------------------------
     def set_learning_rate(self, lr: float) -> None:
@@ -271,16 +299,19 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
         stage = self.stage(n)
         # the bit-range schedule (geta.py:885-900)
         per = self.projection_period_duration
-        self.max_bit_wt = bit_schedule_step(n, self.start_projection_step, self.fix_after_step, per,
+        self.max_bit_wt = bit_schedule_step(n, self.start_projection_step, self._schedule_end, per,
                                             self.bit_reduction, self.min_bit_wt, self.max_bit_wt)
-        self.max_bit_act = bit_schedule_step(n, self.start_projection_step, self.fix_after_step, per,
+        self.max_bit_act = bit_schedule_step(n, self.start_projection_step, self._schedule_end, per,
                                              self.bit_reduction, self.min_bit_act, self.max_bit_act)
         hyper = self._hyper(first_step=False)
+        pr = self._prune
 
         if self._dense:
             ptrs = np.fromiter((self._grad_ptr(nm, p) for nm, p in self._dense), dtype=np.int64,
                                count=len(self._dense))
             live = ptrs != 0
+            if pr is not None:
+                pr.begin_step(n, ptrs, live & ~self._seen, hyper)   # the period boundary: scores and selection
             self._trow[:, 1] = ptrs
             self._trow[:, 5] = (live & ~self._seen).astype(np.int64) << 32   # flags bit 0, lr class 0
             self._ttable.send(self._trow)
@@ -295,11 +326,13 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
             self._qrow[:nq, 3:6] = ptrs
             flags = (fresh * np.array([1, 2, 4])).sum(axis=1).astype(np.int64)
             self._qrow[:nq, 7] = (self._qrow[:nq, 7] & 0xffffffff) | (flags << 32)
-            self._qtable.send(self._qrow)
+            self._qtable.send(self._qrow if pr is None else pr.quant_rows(self._qrow))
             first_fix = stage == _lib.QAT_FIX and not self.fixed
             _lib.qat_quant_step(self._qtable.dev, nq, self._bits, stage, first_fix, hyper,
                                 (self.min_bit_wt, self.max_bit_wt, self.min_bit_act, self.max_bit_act))
             self._qseen[:nq] |= live
+        if pr is not None:
+            pr.finish_step(n, hyper)
         if stage == _lib.QAT_FIX:
             self.fixed = True
         for inv in self._invalidate:
@@ -321,6 +354,7 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
             "quant_moments": self._qmom.detach().clone(), "fixed_bits": self._bits.detach().clone(),
             "seen": self._seen.copy(), "quant_seen": self._qseen.copy(),
             "hyper": {k: v for k, v in self.param_groups[0].items() if k != "params"},
+            **({} if self._prune is None else {"pruning": self._prune.state()}),
         }
 
     @torch.no_grad()
@@ -342,3 +376,414 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
         self.max_bit_wt, self.max_bit_act = int(state["max_bit_wt"]), int(state["max_bit_act"])
         self.fixed = bool(state["fixed"])
         self.param_groups[0].update(state["hyper"])
+        if self._prune is not None:
+            if "pruning" not in state:
+                raise ValueError("the state carries no pruning state")
+            self._prune.load(state["pruning"])
+
+    # ---- pruning ------------------------------------------------------------------------------------------------
+    def _need_prune(self) -> "_PruneState":
+        if self._prune is None:
+            raise ValueError("the optimizer was built without prune_groups")
+        return self._prune
+
+    def pruned_rows(self) -> Dict[str, List[int]]:
+        """{group name: sorted rows committed as pruned}."""
+        return {g.name: sorted(g.pruned) for g in self._need_prune().groups}
+
+    def prune_metrics(self) -> Dict[str, float]:
+        """The fields of the reference's compute_metrics (geta.py:1028-1071). Copies from the device."""
+        return self._need_prune().metrics()
+
+
+# ---- the pruning stages for declared row groups --------------------------------------------------------------------
+# Reference behaviour kept as it is:
+#   * selection (geta.py:172-177): topk(-scores, len(pruned) + n), then np.setdiff1d against the rows already taken,
+#     which returns the rest sorted by index, so a surplus is cut by index and not by score; then [:n];
+#   * the group_divisible refinement (:188-228) with its adjustment of target_num_redundant_groups; rows it gives
+#     back stay in the global list of taken rows, as in the reference, and are never selected again;
+#   * rows committed at a period's last step are written as zeros from the next step on (:1022 runs before :1026);
+#   * the joint branch steps the members without adamw's decay (:1008).
+# Left out: gl_scale (base_hybrid_sparse_optimizer.py:293-333) is computed by the reference and read by nothing.
+# The one difference: `while d_quant < d_quant_lower` (:494) never ends for d_quant == 0; the device cuts it after 861
+# turns (x 1.25 per turn crosses fp32's exponent range) with d = d_quant_upper and gamma = 0.
+# Out of scope: head and head-dim transforms, TRANSPOSE members, auxiliary groups, LoRA scores, the graph tracer and
+# the verbose log files.
+_CRITERIA = ("magnitude", "avg_magnitude", "cosine_similarity", "taylor_first_order", "taylor_second_order")
+
+
+class PruneGroup:
+    """One prunable group set: `members` are parameters sliced along dim 0 (the reference's TensorTransform.BASIC),
+    all of the same shape[0]; `layer` is the QuantizeLinear whose weight quantizer scalars belong to the group. The
+    layer's weight is the quantized member, every other member (its bias) is unquantized."""
+
+    def __init__(self, name: str, layer: nn.Module, members: List[nn.Parameter]):
+        self.name, self.layer, self.members = str(name), layer, list(members)
+
+
+class _GroupState:
+    """A declared group with the optimizer's own state of it (a PruneGroup list may serve several optimizers)."""
+
+    def __init__(self, g: PruneGroup):
+        self.name, self.layer, self.members = g.name, g.layer, list(g.members)
+        self.num_groups = int(self.members[0].shape[0])
+        self.prunable = True
+        self.start = 0                      # global index of row 0 among the prunable groups
+        self.important: List[int] = list(range(self.num_groups))
+        self.active: List[int] = []         # active_redundant_idxes
+        self.pruned: List[int] = []         # pruned_idxes
+
+
+def _check_prune_groups(groups: List[PruneGroup]) -> None:
+    """What the constructor rejects with ValueError, before it looks at the rest of the model."""
+    from .quant_layers import QuantizeLinear
+    seen = set()
+    for g in groups:
+        if not isinstance(g.layer, QuantizeLinear) or getattr(g.layer, "d_quant_wt", None) is None or \
+                getattr(g.layer, "q_m_wt", None) is None:
+            # the reference's compute_gamma_d raises on an empty qm_list
+            raise ValueError(f"group {g.name}: its layer must be a QuantizeLinear with a weight quantizer")
+        if not g.members:
+            raise ValueError(f"group {g.name} has no members")
+        for p in g.members:
+            if not isinstance(p, torch.Tensor) or p.dim() < 1 or p.dtype != torch.float32:
+                raise ValueError(f"group {g.name}: a member must be a float32 tensor sliced along dim 0 "
+                                 f"(got {getattr(p, 'dtype', type(p))})")
+            if not p.is_contiguous():
+                raise ValueError(f"group {g.name}: a member must be contiguous along its rows "
+                                 f"(strides {tuple(p.stride())})")
+            if id(p) in seen:
+                raise ValueError(f"group {g.name}: a parameter appears in two groups")
+            seen.add(id(p))
+        if len({p.shape[0] for p in g.members}) != 1:
+            raise ValueError(f"group {g.name}: members differ in shape[0]: {[tuple(p.shape) for p in g.members]}")
+
+
+def vit_mlp_prune_groups(model: nn.Module) -> List[PruneGroup]:
+    """One PruneGroup per Block: the MLP hidden units, i.e. the rows of fc1.weight and fc1.bias (a zeroed row gives
+    GELU(0) = 0 and an activation code 0, so the matching column of fc2 is inert). For vit_model.py's models and
+    anything with the same blocks[i].mlp.fc1 / fc2 layout."""
+    groups = []
+    for i, blk in enumerate(model.blocks):
+        fc1 = blk.mlp.fc1
+        members = [fc1.weight] + ([fc1.bias] if fc1.bias is not None else [])
+        groups.append(PruneGroup(f"blocks.{i}.mlp", fc1, members))
+    return groups
+
+
+def active_num_redundant_groups(target: int, periods: int) -> List[int]:
+    """Rows to take in each pruning period (geta.py:132-144)."""
+    out, total = [], 0
+    for p in range(periods):
+        if p == periods - 1:
+            out.append(target - total)
+        else:
+            out.append(target // periods)
+            total += out[p]
+    return out
+
+
+def select_redundant(scores: torch.Tensor, taken: List[int], n: int) -> List[int]:
+    """geta.py:172-177, the setdiff1d ordering included."""
+    top = torch.topk(-scores, len(taken) + n)[1].cpu().numpy()
+    return np.setdiff1d(top, taken)[:n].tolist()
+
+
+def refine_by_divisible(g: PruneGroup, group_divisible: int) -> int:
+    """geta.py:188-236 for one group whose `active` holds the fresh selection; returns the adjustment of
+    target_num_redundant_groups."""
+    delta = 0
+    if g.num_groups < group_divisible:
+        g.active.clear()
+        g.pruned.clear()
+    else:
+        trial = len(g.important) - len(g.active)
+        if trial % group_divisible != 0 or trial <= 0:
+            ratio = trial // group_divisible + 1
+            if ratio <= 1 or trial == 0:
+                refined = max(int(group_divisible), 1)
+            else:
+                refined = max(int(ratio * group_divisible), int(group_divisible))
+            refined = min(g.num_groups, refined)
+            n_active = g.num_groups - len(g.pruned) - refined
+            delta = n_active - len(g.active)
+            g.active = g.active[:n_active]
+    g.important = [i for i in g.important if i not in g.active and i not in g.pruned]
+    return delta
+
+
+class _PruneState:
+    """The pruning half of QuantAwareOptimizer: the host bookkeeping of geta.py:904-919, :1024-1026 and the device
+    tables of the qvit_prune_* entry points. Per step: qvit_prune_joint_apply for the members of every group, and
+    while any group has active redundant rows qvit_prune_joint_scalars, _reduce and _finish in front of it; at a
+    period boundary qvit_prune_scores and its finish, followed by the step's one host synchronisation."""
+
+    def __init__(self, opt: "QuantAwareOptimizer", groups: List[PruneGroup], sparsity: float, start: int, steps: int,
+                 periods: int, divisible: int, criteria):
+        self.opt = opt
+        self.groups = groups = [_GroupState(g) for g in groups]
+        self.start, self.steps = start, steps
+        self.periods = int(max(1, periods))
+        self.period = steps // self.periods
+        self.divisible = divisible
+        self.sparsity = sparsity
+        weights = dict(zip(_CRITERIA, [0.2] * 5)) if criteria == "default" else dict(criteria)
+        if set(weights) - set(_CRITERIA):
+            raise ValueError(f"importance_score_criteria: unknown {sorted(set(weights) - set(_CRITERIA))}")
+        self.weights = tuple(float(weights.get(c, 0.0)) for c in _CRITERIA)
+        dense_index = {id(p): i for i, (_, p) in enumerate(opt._dense)}
+        triple_index = {(id(ps[0]), side): i for i, (_, side, ps) in enumerate(opt._triples)}
+        self.member_dense: List[int] = []       # index in opt._dense of every member, in table order
+        self.member_group: List[int] = []
+        self.joint_triples: List[List[int]] = []  # per group: rows of opt._qrow of its layer's sides
+        for g in groups:
+            wq = g.layer.d_quant_wt
+            if (id(wq), 0) not in triple_index or any(id(p) not in dense_index for p in g.members):
+                raise ValueError(f"group {g.name}: its layer and members must belong to the optimizer's model")
+            self.joint_triples.append([triple_index[(id(wq), 0)]] +
+                                      ([triple_index[(id(g.layer.d_quant_act), 1)]]
+                                       if getattr(g.layer, "d_quant_act", None) is not None else []))
+        # prunable groups first, in the given order: their rows are the global indices 0 .. total_num_groups - 1
+        self.total_num_groups = 0
+        for g in groups:
+            g.prunable = g.num_groups > divisible       # base_hybrid_sparse_optimizer.py:118-125
+            if g.prunable:
+                g.start = self.total_num_groups
+                self.total_num_groups += g.num_groups
+        self.target = int(self.total_num_groups * min(sparsity, 0.999))
+        self.per_period = active_num_redundant_groups(self.target, self.periods)
+        self.curr_period = 0
+        self.taken: List[int] = []          # the reference's pruned_group_idxes (global)
+        self.order = [i for i, g in enumerate(groups) if g.prunable] + \
+                     [i for i, g in enumerate(groups) if not g.prunable]
+
+        dev = opt.device
+        ng = len(groups)
+        self._grow = np.zeros((ng, _lib.PRUNE_GROUP_BYTES // 8), dtype=np.int64)
+        mrows = []
+        for gi, g in enumerate(groups):
+            ly = g.layer
+            t = getattr(ly, "t_quant_wt", None)
+            self._grow[gi, 0:3] = (ly.d_quant_wt.data_ptr(), ly.q_m_wt.data_ptr(), 0 if t is None else t.data_ptr())
+            self._grow[gi, 3] = len(mrows) | (len(g.members) << 32)
+            elems = 0
+            for p in g.members:
+                di = dense_index[id(p)]
+                width = p.numel() // g.num_groups
+                elems += width
+                mrows.append([p.data_ptr(), 0, 0 if opt._m[di] is None else opt._m[di].data_ptr(),
+                              0 if opt._v[di] is None else opt._v[di].data_ptr(), width,
+                              1 if p is ly.weight else 0])
+                self.member_dense.append(di)
+                self.member_group.append(gi)
+            self._grow[gi, 6] = elems
+        self._mrow = np.array(mrows, dtype=np.int64)
+        self.nmembers = len(mrows)
+        self.nrows = sum(g.num_groups for g in groups)
+        self._gtable = _Upload(ng, self._grow.shape[1], dev)
+        self._mtable = _Upload(self.nmembers, self._mrow.shape[1], dev)
+        self._itable = _Upload(self.nrows, _lib.PRUNE_ITEM_BYTES // 8, dev)    # every row, prunable groups first
+        self._rtable = _Upload(self.nrows, _lib.PRUNE_ITEM_BYTES // 8, dev)    # the active redundant rows
+        self._jtable = _Upload(2 * ng, opt._qrow.shape[1], dev)
+        self._sums = torch.zeros((max(self.nrows, 1), 3), dtype=torch.float64, device=dev)
+        self._scores = torch.zeros(max(self.nrows, 1), dtype=torch.float32, device=dev)
+        self._partials = torch.zeros((max(self.nrows, 1), 6), dtype=torch.float64, device=dev)
+        self.gamma = torch.zeros(ng, dtype=torch.float32, device=dev)
+        self.info = torch.full((ng,), -1, dtype=torch.int32, device=dev)
+        self._nred = 0
+        self._jrow = np.zeros((2 * ng, opt._qrow.shape[1]), dtype=np.int64)
+        self._qsend = np.zeros_like(opt._qrow)
+        self._member_group = np.asarray(self.member_group)
+        self._tables()
+
+    # ---- tables ---------------------------------------------------------------------------------------------------
+    def _tables(self) -> None:
+        """The group, item and joint quantizer rows from the host lists (rebuilt when the lists change)."""
+        items, red = [], []
+        self._joint_rows: List[int] = []
+        for gi in self.order:
+            g = self.groups[gi]
+            state = np.zeros(g.num_groups, dtype=np.int64)
+            state[g.active] = _lib.PRUNE_REDUNDANT
+            state[g.pruned] = _lib.PRUNE_PRUNED
+            rows = np.arange(g.num_groups, dtype=np.int64)
+            items.append(np.stack([gi | (rows << 32), state], axis=1))
+            joint = g.prunable and len(g.active) > 0
+            self._grow[gi, 4] = g.num_groups | (int(joint) << 32)
+            begin = sum(len(r) for r in red)
+            self._grow[gi, 5] = (begin | (len(g.active) << 32)) if joint else 0
+            if joint:
+                act = np.asarray(g.active, dtype=np.int64)
+                red.append(np.stack([gi | (act << 32), np.full(len(act), _lib.PRUNE_REDUNDANT, np.int64)], axis=1))
+                self._joint_rows.extend(self.joint_triples[gi])
+        self._items = np.concatenate(items) if items else np.zeros((0, 2), np.int64)
+        self._nred = sum(len(r) for r in red)
+        self._red = np.zeros((max(self.nrows, 1), 2), dtype=np.int64)
+        if red:
+            self._red[:self._nred] = np.concatenate(red)
+        self._dirty = True   # the row lists go to the device when they change, not every step
+
+    def quant_rows(self, qrow: np.ndarray) -> np.ndarray:
+        """qvit_qat_quant_step's table with the joint layers' triples struck out: qvit_prune_joint_scalars has them."""
+        if not self._joint_rows:
+            return qrow
+        self._qsend[...] = qrow
+        self._qsend[self._joint_rows, 0] = 0
+        return self._qsend
+
+    # ---- the step -------------------------------------------------------------------------------------------------
+    def _boundary(self, n: int) -> bool:
+        return (n >= self.start and self.curr_period < self.periods and self.period != 0
+                and (n - self.start - 1) % self.period == 0)
+
+    def commit(self) -> None:
+        """commit_redundant_idxes (geta.py:238-248)."""
+        for g in self.groups:
+            if g.prunable:
+                g.pruned.extend(g.active)
+                g.active = []
+                g.important = [i for i in range(g.num_groups) if i not in g.pruned]
+
+    def begin_step(self, n: int, grad_ptrs: np.ndarray, fresh: np.ndarray, hyper: tuple) -> None:
+        self._mrow[:, 1] = grad_ptrs[self.member_dense]
+        self._mrow[:, 5] = (self._mrow[:, 5] & 0xffffffff) | (fresh[self.member_dense].astype(np.int64) << 32)
+        if self._boundary(n):
+            self._select(hyper)
+        # before any launch of this step: the joint stage reads every member's gradient (compute_gamma_d would raise)
+        for gi, g in enumerate(self.groups):
+            if g.prunable and g.active and (self._mrow[self._member_group == gi, 1] == 0).any():
+                raise QvitError(f"group {g.name}: every member needs a gradient in the joint stage")
+
+    def _select(self, hyper: tuple) -> None:
+        # geta.py:905-919: commit, the scores (this step's grad_variant, the parameters before the update), selection
+        self.commit()
+        self._tables()
+        self._send()
+        ng = len(self.groups)
+        _lib.prune_scores(self._gtable.dev, ng, self._mtable.dev, self.nmembers, self._itable.dev,
+                          self.total_num_groups, self._sums, self.weights, self._scores, hyper)
+        chosen = select_redundant(self._scores[:self.total_num_groups], self.taken, self.per_period[self.curr_period])
+        self.taken.extend(chosen)
+        for g in self.groups:
+            if g.prunable:
+                ids = np.arange(g.start, g.start + g.num_groups)
+                g.active = (np.intersect1d(chosen, ids) - g.start).tolist()
+                self.target += refine_by_divisible(g, self.divisible)
+        self.curr_period += 1
+        self._tables()
+
+    def _send(self) -> None:
+        self._mtable.send(self._mrow)
+        if self._dirty:
+            self._gtable.send(self._grow)
+            self._itable.send(self._items)
+            self._rtable.send(self._red)
+            self._dirty = False
+
+    def finish_step(self, n: int, hyper: tuple) -> None:
+        opt = self.opt
+        ng = len(self.groups)
+        t_in = (n - self.start) % self.period if self.period else 0
+        self._send()
+        if self._nred:
+            nj = len(self._joint_rows)
+            self._jrow[:nj] = opt._qrow[self._joint_rows]
+            self._jrow[nj:] = 0
+            self._jtable.send(self._jrow)
+            _lib.prune_joint_scalars(self._jtable.dev, nj, hyper, opt.min_bit_act, opt.max_bit_act)
+            _lib.prune_joint_reduce(self._gtable.dev, ng, self._mtable.dev, self.nmembers, self._rtable.dev,
+                                    self._nred, self._partials, hyper)
+            _lib.prune_joint_finish(self._gtable.dev, ng, self._partials, self._nred, opt.param_groups[0]["lr"],
+                                    self.period, t_in, opt.min_bit_wt, opt.max_bit_wt, self.gamma, self.info)
+        _lib.prune_joint_apply(self._gtable.dev, ng, self._mtable.dev, self.nmembers, self._itable.dev, self.nrows,
+                               self.gamma, hyper)
+        if self.period and n >= self.start and t_in == self.period - 1:   # geta.py:1024-1026
+            self.commit()
+            self._tables()
+
+    # ---- state and metrics ----------------------------------------------------------------------------------------
+    def state(self) -> dict:
+        return {"group_names": [g.name for g in self.groups],
+                "pruned_idxes": [list(g.pruned) for g in self.groups],
+                "active_redundant_idxes": [list(g.active) for g in self.groups],
+                "important_idxes": [list(g.important) for g in self.groups],
+                "pruned_group_idxes": list(self.taken), "curr_pruning_period": self.curr_period,
+                "target_num_redundant_groups": self.target}
+
+    def load(self, st: dict) -> None:
+        if st["group_names"] != [g.name for g in self.groups]:
+            raise ValueError("the pruning state belongs to other groups")
+        for g, pr, ac, im in zip(self.groups, st["pruned_idxes"], st["active_redundant_idxes"],
+                                 st["important_idxes"]):
+            g.pruned, g.active, g.important = list(pr), list(ac), list(im)
+        self.taken = list(st["pruned_group_idxes"])
+        self.curr_period = int(st["curr_pruning_period"])
+        self.target = int(st["target_num_redundant_groups"])
+        self._tables()
+
+    @torch.no_grad()
+    def metrics(self) -> Dict[str, float]:
+        m = dict(norm_params=0.0, norm_important_groups=0.0, norm_redundant_groups=0.0, num_zero_groups=0,
+                 num_important_groups=0, num_redundant_groups=0)
+        for g in self.groups:
+            if not g.prunable:
+                continue
+            sq = sum(p.detach().reshape(g.num_groups, -1).double().pow(2).sum(dim=1) for p in g.members)
+            norm = sq.sqrt().cpu().numpy()
+            red = g.active + g.pruned
+            m["num_zero_groups"] += int(np.sum(norm == 0))
+            m["norm_params"] += float(np.sum(norm))
+            m["norm_important_groups"] += float(np.sum(norm[g.important]))
+            m["norm_redundant_groups"] += float(np.sum(norm[red]))
+            m["num_important_groups"] += len(g.important)
+            m["num_redundant_groups"] += len(red)
+        m["group_sparsity"] = m["num_zero_groups"] / float(self.total_num_groups + 1e-8)
+        return m
+
+
+def _resized_linear(src: nn.Linear, weight: torch.Tensor, bias: Optional[torch.Tensor]) -> nn.Linear:
+    """A layer of src's kind around the given weight and bias, src's quantizer scalars and clip values carried over."""
+    from .quant_layers import QuantizeLinear
+    out_f, in_f = weight.shape
+    if isinstance(src, QuantizeLinear):
+        new = QuantizeLinear(in_f, out_f, bias=bias is not None, quant_type=src.quant_type, quant_mode=src.quant_mode)
+        new.weight_clip_val, new.act_clip_val = src.weight_clip_val, src.act_clip_val
+    else:
+        new = nn.Linear(in_f, out_f, bias=bias is not None)
+    new = new.to(device=weight.device, dtype=weight.dtype)
+    new.weight.data.copy_(weight)
+    new.weight.requires_grad_(src.weight.requires_grad)
+    if bias is not None:
+        new.bias.data.copy_(bias)
+        new.bias.requires_grad_(src.bias.requires_grad)
+    for side in _SIDES:
+        for sc in _SCALARS:
+            a, b = getattr(src, f"{sc}_{side}", None), getattr(new, f"{sc}_{side}", None)
+            if a is not None and b is not None:
+                b.data.copy_(a.data)
+                b.requires_grad_(a.requires_grad)
+    new.train(src.training)
+    if callable(getattr(new, "invalidate", None)):
+        new.invalidate()
+    return new
+
+
+@torch.no_grad()
+def compress_pruned_mlp(model: nn.Module) -> nn.Module:
+    """Removes every all-zero fc1 row (weight row and bias entry both zero) of every blocks[i].mlp together with its
+    fc2 column, in place, and returns the model: this project's counterpart of the reference's construct_subnet for
+    this one structure. The quantizer scalars are carried over and the plans start afresh. An optimizer built over
+    the model before the call no longer matches it."""
+    for blk in model.blocks:
+        fc1, fc2 = blk.mlp.fc1, blk.mlp.fc2
+        dead = (fc1.weight == 0).all(dim=1)
+        if fc1.bias is not None:
+            dead &= fc1.bias == 0
+        keep = (~dead).nonzero().flatten()
+        if keep.numel() == fc1.out_features:
+            continue
+        if keep.numel() == 0:
+            raise ValueError("compress_pruned_mlp: a block's MLP has no hidden unit left")
+        blk.mlp.fc1 = _resized_linear(fc1, fc1.weight[keep], None if fc1.bias is None else fc1.bias[keep])
+        blk.mlp.fc2 = _resized_linear(fc2, fc2.weight[:, keep], fc2.bias)
+    return model
