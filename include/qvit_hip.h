@@ -150,6 +150,13 @@ const char* qvit_version(void);
  *   codes  : int8 [rows][ldc]; columns [cols, kpad) are written with 0 (kpad <= ldc, kpad % 16 == 0)
  *   qtype  : QVIT_QT_*; levels is only read for QVIT_QT_ULTRA_ACT.
  * Codes saturate at +-127 (the caller rejects layers whose level count exceeds 127).
+ * Special values: a NaN gives code 0; +-Inf and +-FLT_MAX give +-min(L, 127), L the saturation code rne(p_sat / d);
+ * +-0 and a finite value whose quotient rounds to 0 give 0; a negative q_m saturates every non-zero value. With
+ * QVIT_QT_ULTRA_ACT a NaN gives 0 (fmax(NaN, 0)), -Inf 0 and +Inf `levels`. The codes are the same on the guarded fast
+ * path and under QVIT_QT_FORCE_CAREFUL, on the 16-byte and the scalar loads, and for a nonlinear quantizer on values
+ * below 1e-30 (denormals included), which always take the careful sequence; a step d below 2^-128, whose reciprocal
+ * is not finite, sends every element there. An element changes its own code only. The same rules hold for every
+ * int8 code output of this header (tests/test_gpu_special_values.py).
  * Replaces quant_layers.py:356-381 (+ :41-69 / :137-161) and quant_ultra.py:66-73.
  */
 int qvit_quantize_act_i8(const float* x, int64_t rows, int64_t cols, int64_t ldx,
@@ -159,6 +166,9 @@ int qvit_quantize_act_i8(const float* x, int64_t rows, int64_t cols, int64_t ldx
 /*
  * Fake-quant fp32 values exactly as the reference returns them (y = sgn(x) * (d * rne(...)),
  * saturation and zero masks in the reference's order). Elementwise over n contiguous floats.
+ * Special values: as the reference on every input: a NaN comes out a NaN (sign(NaN) * output), +-Inf and +-FLT_MAX
+ * +-d L, +-0 gives 0. QVIT_QT_ULTRA_ACT keeps NaN -> 0 (round(clamp(x, 0, 1) n) / n with fmax(NaN, 0) = 0). The codes
+ * behind the values (qvit_quantize_act_i8, qvit_quant_error) keep NaN -> 0.
  * Replaces SymQuantizerLinear/NonLinear.forward (quant_layers.py:41-69,137-161) when a layer's
  * levels do not fit the integer path.
  */
@@ -400,6 +410,9 @@ int qvit_gelu_f32(const float* x, int64_t n, float* y, hipStream_t stream);
  * qvit_gelu_quant_i8: codes = quantize(GELU(h)), byte for byte qvit_quantize_act_i8(qvit_gelu_f32(h)); arguments as
  * qvit_quantize_act_i8.
  *
+ * Special values: the codes of qvit_quantize_act_i8 at GELU(h) as torch computes it: GELU(NaN) and GELU(-Inf) = -Inf * 0
+ * are NaN (code 0), GELU(+Inf) = +Inf (the saturation code); fast and QVIT_QT_FORCE_CAREFUL agree.
+ *
  * qvit_gelu_quant_backward: qvit_quant_backward at a = GELU(h) followed by GELU's own derivative:
  * grad_h = (Phi(h) + h phi(h)) gy with Phi from the forward's erf; grad_scalars, workspace, alignment, aliasing
  * (grad_h may be grad_y) and n == 0 as qvit_quant_backward. Moves 3 n 4 bytes.
@@ -471,6 +484,10 @@ int qvit_pad_bias(const float* bias, int64_t n, float* out, int64_t npad, hipStr
  *   codes  : int8 [B*OH*OW][ldc], row (b, oh, ow), column (c, ih, iw) = c*kh*kw + ih*kw + iw;
  *            columns [C*kh*kw, kpad) zero. Zero-padding of the image quantizes to code 0, as in
  *            the reference (quantize_act runs before F.conv2d pads).
+ *   Special values: a NaN pixel gives code 0 and a +-Inf pixel the saturation code in exactly the entries that tap
+ *   it (rows (b, oh, ow) and columns (c, ih, iw) with oh sh - ph + ih dh = y, ow sw - pw + iw dw = x); no other entry
+ *   changes. qvit_im2col_u8_i8 takes bytes and a caller-made code table: a NaN or Inf in the normaliser's
+ *   value_table is the caller's qvit_quantize_act_i8 call, nothing is defined here beyond that.
  *   OH = (H + 2 ph - dh (kh - 1) - 1) / sh + 1, OW alike; a padded image smaller than the dilated kernel on
  *   either axis is QVIT_EINVAL at every stride.
  */
@@ -518,6 +535,10 @@ int qvit_u8_normalize_f32(const uint8_t* img, int64_t B, int64_t C, int64_t H, i
  *            with cols % 4, ldx % 4 or a base off 16 bytes take a scalar kernel, as do cols > 2048).
  *   code_table : nullable, 16-B aligned; a qvit_epi_table_build table (QVIT_EPI_I8 semantics) of the
  *            same quantizer, used only if valid and <= 2046 buckets (results never depend on it).
+ * Special values: a NaN or +-Inf anywhere in a row makes the row's mean, and with it every y of the row, NaN: all
+ * `cols` codes of that row are 0 (its padding stays 0), on every kernel arm, with and without the code table, and in
+ * the T32 order. Every other row is bit-identical to what it is without the special value (a workgroup holds four
+ * rows; nothing is shared between them).
  */
 int qvit_layernorm_quant_i8(const float* x, int64_t rows, int64_t cols, int64_t ldx,
                             const float* gamma, const float* beta, float eps,
@@ -538,6 +559,10 @@ int qvit_layernorm_quant_i8(const float* x, int64_t rows, int64_t cols, int64_t 
  *   C      : fp32 / int8 / int32 [M][ldc] per epilogue; ldc % 4 == 0 (fp32/int32), % 16 (int8).
  *   For QVIT_EPI_I8*: the next layer's quantizer (out_qtype, out_d, out_qm, out_t, out_levels) and an
  *   optional code table (qvit_epi_table_build, NULL -> per-element evaluation).
+ * Special values: the activations are codes, so a NaN or Inf enters through bias[n] or (QVIT_EPI_F32_RESID) C[m][n].
+ * A bias entry changes its own column only: QVIT_EPI_F32 / _RESID write NaN, +Inf, -Inf there; QVIT_EPI_I8 writes 0,
+ * L, -L and QVIT_EPI_I8_GELU 0, L, 0 (GELU(-Inf) is NaN), the same for QVIT_W4, W8, W4R and W8R and with or without the
+ * code table. A NaN in C[m][n] stays that one element.
  */
 int qvit_gemm(const int8_t* A, int64_t M, int64_t K, int64_t lda,
               const void* Wp, int wfmt, int64_t N, int64_t npad,
@@ -562,6 +587,8 @@ int qvit_gemm(const int8_t* A, int64_t M, int64_t K, int64_t lda,
  *   as qvit_gemm on the row-major codes, byte for byte. Shapes: qvit_gemm_a32_fits (wfmt QVIT_W4, epilogue
  *   QVIT_EPI_I8 / QVIT_EPI_I8_GELU, N == npad == 3072, K == 768 or 1024) returns 1, else the call is QVIT_EINVAL.
  *   C: int8 [M][ldc], ldc % 16 == 0, 16-byte aligned.
+ * Special values: qvit_layernorm_quant_i8_t32 as qvit_layernorm_quant_i8 (a poisoned row: all codes 0), qvit_gemm_a32 as
+ * qvit_gemm (a bias entry changes its column only; same codes direct and tabled).
  */
 int qvit_layernorm_quant_i8_t32(const float* x, int64_t rows, int64_t cols, int64_t ldx, const float* gamma,
                                 const float* beta, float eps, int qtype, const float* d_quant, const float* q_m,
@@ -587,6 +614,9 @@ int qvit_gemm_a32(const int8_t* A, int64_t M, int64_t K, const void* Wp, int wfm
  *            (splits * M * npad floats) are then summed in a fixed order; NULL -> no split.
  * fp32-GEMM accuracy: X is split into three bf16 terms whose sum is X exactly, every product with a code is
  * exact in fp32, accumulation is fp32 (the order of the K-term sum differs from the reference's GEMM).
+ * Special values: a NaN or Inf in X[m][k] changes row m of Y only, with or without the split-K workspace (the
+ * partials are per row); a NaN makes Y[m][n] NaN for every n, as the exact product does (NaN * 0 is NaN). What an Inf
+ * leaves in its row is not defined (the bf16 split of Inf has NaN terms).
  */
 int qvit_gemm_wonly(const float* X, int64_t M, int64_t K, int64_t ldx, const void* Wp, int wfmt,
                     int64_t N, int64_t npad, const float* d_wt, const float* bias, float* Y, int64_t ldy,
@@ -720,6 +750,9 @@ int qvit_conv_wonly_bn_act(const float* X, int64_t B, int64_t C, int64_t H, int6
  *              running concurrently on another stream.
  * The last of a row block's npad / 256 workgroups runs the LayerNorm of its rows; the residual rows are written
  * through (sc1) and read back with sc1 loads behind an agent-scope counter.
+ * Special values: a NaN in C[m][n] (or a bias column) stays where qvit_gemm(QVIT_EPI_F32_RESID) leaves it, and row m's
+ * codes are the poisoned-row codes of qvit_layernorm_quant_i8 (all 0), with and without ln_table. Every other row of C
+ * and of the codes is bit-identical: the hand-off between workgroups is per 128-row block and carries no values.
  */
 int qvit_gemm_resid_ln(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, int wfmt,
                        int64_t N, int64_t npad, const float* d_act, const float* d_wt, const float* bias,
@@ -735,6 +768,9 @@ int qvit_gemm_resid_ln(const int8_t* A, int64_t M, int64_t K, int64_t lda, const
  * nb uniform buckets of width w starting at v_lo (w must be below the smallest distance between two
  * of its change points, and the function constant beyond both ends). The device builds it by bisection
  * with the epilogue's own arithmetic and validates it; qvit_gemm uses it only if valid (else the
+ * Bucket j holds the v with rne((v - v_lo) / w) == j, clamped to [0, nb - 1]; a NaN reads bucket 0. Bucket 0 must hold a
+ * single code (start the range a bucket below the first change point): its spare byte then carries the direct path's
+ * code of a NaN (0). A table whose bucket 0 has a change point is invalid.
  * direct per-element evaluation runs), so results never depend on the choice of (v_lo, w, nb).
  */
 #define QVIT_EPI_TABLE_MAX_NB 3800
@@ -756,6 +792,11 @@ int qvit_epi_table_build(int epilogue, int out_qtype, const float* out_d, const 
  *              QVIT_ATT_I8  -> int8 codes of the next layer's activation quantizer
  *              (out_qtype, out_d, out_qm, out_t, out_levels as in qvit_gemm), ldo % 4 == 0.
  * fp32 matmuls are formed from fp16 hi/lo products with fp32 accumulation (~2^-22 relative error).
+ * Special values (qvit_attention and qvit_attention_split): a NaN or Inf in q, k or v of one (image, head) changes the
+ * outputs of that (image, head) only; every other block is bit-identical. A NaN in q[i] makes out[i][:] of the block
+ * NaN, a NaN in v[j][d] makes out[:][d] of the block NaN, exactly where the exact product is NaN. What +-Inf leaves
+ * inside its block is not defined (inf - inf in the softmax). QVIT_ATT_I8: a NaN output has code 0, direct and
+ * through the code table alike.
  */
 /*
  * UltraNet (reference `4-bit quantization/`: quant_ultra.py:8-91, mymodel.py:23-144).

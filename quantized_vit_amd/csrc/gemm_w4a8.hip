@@ -243,12 +243,18 @@ __global__ void epi_table_kernel(int gelu, int out_qtype, const float* out_d, co
   e.lo = to_i8_sat(cs);
   e.hi = to_i8_sat(ce);
   e.pad = 0;
-  if (j == 0 && cs == ce) {
+  if (j == 0) {
     // NaN: the index formula's med3 sends it to bucket 0 and `v >= thr` is false for it, so it reads `lo`. With F
     // constant over the bucket, every ordered v (-inf included) passes thr = -inf and reads `hi`, which leaves `lo`
-    // for the direct quantizer's code of NaN (0). (A bucket 0 with a change point keeps NaN on its lower code.)
-    e.thr = -INFINITY;
-    e.lo = to_i8_sat(epi_F(NAN, gelu, qp));
+    // for the direct quantizer's code of NaN (0). A bucket 0 with a change point needs `lo` for its own lower code
+    // and would give NaN that code (-L), not the direct path's 0: such a table is invalid, and the epilogues
+    // evaluate directly (epilogue_table_geometry starts the range one bucket below the first change point).
+    if (cs != ce) {
+      ok = false;
+    } else {
+      e.thr = -INFINITY;
+      e.lo = to_i8_sat(epi_F(NAN, gelu, qp));
+    }
   }
   ent[j] = e;
   if (!ok) atomicAnd(&hdr->valid, 0);

@@ -60,7 +60,11 @@ __global__ __launch_bounds__(kThreads) void fake_quant_kernel(const float* __res
   const QParams p = load_qparams(qtype, d, qm, t, levels);
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
-    y[i] = fake_quant_value(x[i], p);
+    // the reference's last step is sign(x) * output (:68, :160), and sign(NaN) is NaN: a NaN passes through. The
+    // codes (quant_code, shared with the int8 kernels and qvit_quant_error) keep NaN -> 0, as does ULTRA_ACT.
+    const float xv = x[i];
+    const float v = fake_quant_value(xv, p);
+    y[i] = (xv == xv || p.qtype == QVIT_QT_ULTRA_ACT) ? v : xv;
   }
 }
 

@@ -50,6 +50,9 @@ QVIT_DEV QParams load_qparams(int qtype, const float* d, const float* qm, const 
   p.qm = *qm;
   p.t = (t != nullptr) ? *t : 1.f;
   p.inv_d = 1.f / p.d;
+  // a denormal step below 2^-128 has no finite reciprocal: the fast quotient would be inf where the careful one
+  // (an IEEE division) is finite, so every element takes the careful path
+  if (!(fabsf(p.inv_d) < 3.0e38f)) p.careful = 1;
   if (p.qtype == QVIT_QT_LINEAR) {
     p.L = rintf(fabsf(p.qm) / p.d);
   } else {

@@ -879,6 +879,9 @@ def epilogue_table_geometry(qtype: int, d: float, qm: float, t: float, level: fl
     else:
         v_hi, v_lo = x_sat * 1.02 + 1e-3, -(x_sat * 1.02 + 1e-3)
         w = 0.8 * min_gap
+    # one more bucket below the first change point: bucket 0 then holds one code only, which frees its `lo` byte for
+    # the code of a NaN (the device rejects a table whose bucket 0 has a change point)
+    v_lo -= w
     nb = int(math.ceil((v_hi - v_lo) / w)) + 1
     if nb > _lib.EPI_TABLE_MAX_NB:
         return None

@@ -106,13 +106,17 @@ def test_quantize_act_boundaries(dev, ps):
 
 @SETS
 def test_fake_quant_boundaries(dev, ps):
-    """d * code rounded once (ULTRA_ACT: code / levels)."""
+    """d * code rounded once (ULTRA_ACT: code / levels). A NaN passes through the linear and nonlinear quantizers as
+    in the reference (sign(NaN) * output); its code, and ULTRA_ACT's value, stay 0."""
     x = _vals(ps)
     qt, d, qm, t, lv = _q(ps, dev)
     y = _lib.fake_quant_f32(x.to(dev), qt, d, qm, t, lv).cpu()
     k, mask = _want(x, ps)
     want = k.float() / float(ps.levels) if ps.qt == V.ULTRA_ACT else V._f32(ps.d) * k.float()
-    assert torch.equal(y[~mask], want[~mask]), (y[~mask] != want[~mask]).nonzero()[:4].tolist()
+    nan = torch.isnan(x) if ps.qt != V.ULTRA_ACT else torch.zeros_like(mask)
+    assert bool(nan.any()) == (ps.qt != V.ULTRA_ACT) and torch.equal(torch.isnan(y), nan)
+    keep = ~mask & ~nan
+    assert torch.equal(y[keep], want[keep]), (y[keep] != want[keep]).nonzero()[:4].tolist()
 
 
 @SETS
