@@ -22,7 +22,8 @@
  *                             OTO/optimizer/geta.py:571-804, :873-943 and base_optimizer.py:40-86: the warm-up, bit-range
  *                             projection and fix stages of the GETA optimizer as one multi-tensor launch for the dense
  *                             tensors and one for the quantizer scalars, with no .item() on the way.
- *   qvit_prune_scores / qvit_prune_scores_finish / qvit_prune_joint_scalars / qvit_prune_joint_reduce /
+ *   qvit_prune_scores / qvit_prune_scores_fold / qvit_prune_scores_finish / qvit_prune_joint_scalars /
+ *   qvit_prune_joint_reduce /
  *   qvit_prune_joint_finish / qvit_prune_joint_apply
  *                             OTO/optimizer/geta.py:167-248, :281-521, :944-1026 and base_hybrid_sparse_optimizer.py:
  *                             194-291: the saliency scores and the joint pruning and quantization stage for declared
@@ -311,21 +312,33 @@ int qvit_qat_quant_step(const void* quants, int nquants, int32_t* bits, int stag
  *
  * Device tables (the host fills them as int64 rows):
  *   groups  : ngroups descriptors of 64 bytes: { float* d; const float* q_m; const float* t; int32_t member_begin,
- *             member_count; int32_t rows; int32_t joint; int32_t red_begin, red_count; int64_t elems; int64_t
- *             reserved; }: the weight quantizer scalars of the group's layer (t NULL: the linear type), its members
- *             [member_begin, member_begin + member_count) of `members`, its row count, joint = 1 while it has active
- *             redundant rows, the range of its redundant rows in the reduce's item list, and elems = the elements of
- *             one row over all members.
+ *             member_count; int32_t rows; int32_t joint; int32_t red_begin, red_count; int64_t elems; int32_t
+ *             sections, unit_rows; }: the weight quantizer scalars of the group's layer (t NULL: the linear type), its
+ *             members [member_begin, member_begin + member_count) of `members`, its row count, joint = 1 while it has
+ *             active redundant rows, the range of its redundant rows in the reduce's item list, elems = the elements
+ *             of one unit over all members, and the geometry of a unit: sections and unit_rows both 0 (or 1): a unit
+ *             is one row; else a member has sections x units x unit_rows rows and unit h is the rows (s units + h)
+ *             unit_rows + j for s in [0, sections), j in [0, unit_rows) (head h of a qkv projection: sections = 3,
+ *             unit_rows = the head dim).
  *   members : nmembers descriptors of 48 bytes: { float* p; const float* grad; float* m; float* v; int64_t width;
  *             int32_t quantized; int32_t flags; }: qvit_qat_step's tensor descriptor with the row width in place of
  *             numel; quantized = 1 for the layer's weight; flags bit 0: this tensor's first step. A member whose
  *             four pointers are 16-byte aligned and whose width is a multiple of 4 moves 16 bytes at a time, any
  *             other one element at a time: same bits.
- *   items   : nitems entries of 16 bytes: { int32_t group, row, state, reserved; }, state 0 important, 1 active
- *             redundant, 2 pruned. A wave owns one item. Items that name no group or no row of it are skipped.
+ *   items   : nitems entries of 16 bytes: { int32_t group, row, state, link; }, state 0 important, 1 active
+ *             redundant, 2 pruned: the state of the row's unit. A wave owns one item, a physical row in every geometry.
+ *             link = the row's unit, 0 where a unit is one row. Items that name no group or no row of it are skipped.
+ *   units   : (qvit_prune_scores_fold and the finish behind it) the same 16 bytes per unit: row = the unit's index
+ *             in its group, link = the index in `items` of row 0 of that group, whose rows follow it in ascending
+ *             order.
  *
  * qvit_prune_scores: sums[3 i .. 3 i + 2] = sum p^2, sum g^2, sum p g of item i's row over the members, g the
  *   gradient variant, in double (a member without grad adds to sum p^2 only).
+ * qvit_prune_scores_fold: unit_sums[3 u ..] = the three sums of unit u added up over its rows' entries of `sums`,
+ *   section-major, row ascending, by one thread: the same bits in every run. A unit whose group, index or rows do not
+ *   agree with the tables (the row items' group, row and link are compared) gets zeros. Only needed where some group
+ *   has units of several rows; the finish then takes `units` and `unit_sums` for items and sums, and scores has one
+ *   entry per unit.
  * qvit_prune_scores_finish: scores[i] = sum_c w_c score_c(i) / (sqrt(1e-8 + sum_j score_c(j)^2) + 1e-8) over the
  *   criteria magnitude = sqrt(sum p^2), avg_magnitude = magnitude / (elems + 1e-6), cosine = sum p g / (|p| + 1e-8) /
  *   (|g| + 1e-8) + 1, taylor1 = |sum p g|, taylor2 = 0.5 taylor1^2, in that order; a weight of 0 leaves a criterion
@@ -333,7 +346,7 @@ int qvit_qat_quant_step(const void* quants, int nquants, int32_t* bits, int stag
  * qvit_prune_joint_scalars: quants as qvit_qat_quant_step's. A weight-side triple: q_m and t step at lr_quant
  *   without decay, d only moves its moments (geta.py:952-960); an activation-side triple takes the range stage's
  *   activation pass (:667-721): one step at lr_quant, then d clamped into [d(max_bit_act), d(min_bit_act)].
- * qvit_prune_joint_reduce: items lists the active redundant rows, a group's rows contiguous at [red_begin, red_begin +
+ * qvit_prune_joint_reduce: items lists the rows of the active redundant units, a group's rows contiguous at [red_begin, red_begin +
  *   red_count); partials[6 i ..] = <clip, g>, |clip|^2, |g|^2, <res, g>, |res|^2, sum clip of that row, clip and res
  *   by _clip_helper and _residual_helper (:821-850) for the quantized member, clip = p and res = 0 for the others.
  * qvit_prune_joint_finish: one workgroup per group folds its partials in index order and evaluates compute_gamma_d
@@ -343,13 +356,14 @@ int qvit_qat_quant_step(const void* quants, int nquants, int32_t* bits, int stag
  *   the loop was cut after 861 turns (fp32's whole exponent range): d = d_quant_upper, gamma = 0, where the reference
  *   would not end; -1 for a group that is not joint). lr is the host's double; period and t_in_period give the
  *   schedule 1 - (period - t - 1) / (period - t).
- * qvit_prune_joint_apply: items lists every row of every group. Joint groups: on redundant rows p -= gamma *
+ * qvit_prune_joint_apply: items lists every row of every group. Joint groups: on the rows of redundant units p -= gamma *
  *   quantize(p) (weight; _quantize_helper :806-819 with the new d) or gamma * p (others), then p -= lr g without
  *   adamw's decay (:982-1008); other groups: the dense step. Moments as qvit_qat_step leaves them; pruned rows are
  *   written as zeros (base_hybrid_sparse_optimizer.py:194-211).
  * Order of the checks (part of the ABI), for scores, joint_reduce and joint_apply: a table or the output NULL
  * (QVIT_ENULL); any of them off 8 bytes (QVIT_EALIGN); a count < 0 or nitems > 2^31 - 1 (QVIT_EINVAL); unknown variant
- * (QVIT_EINVAL); a zero count is a no-op success. scores_finish: NULL; groups, items or sums off 8 bytes or scores
+ * (QVIT_EINVAL); a zero count is a no-op success. scores_fold: a table, sums or unit_sums NULL; any of the five off 8
+ * bytes; a count < 0, nitems or nunits > 2^31 - 1; ngroups or nunits zero is a no-op success. scores_finish: NULL; groups, items or sums off 8 bytes or scores
  * off 4; counts. joint_scalars: NULL; off 8 bytes; nquants < 0; variant; the bit range. joint_finish: NULL; groups or
  * partials off 8 bytes or gamma or info off 4; counts; period < 1 or t_in_period outside [0, period); the bit range.
  */
@@ -358,6 +372,8 @@ int qvit_prune_scores(const void* groups, int ngroups, const void* members, int 
                       float first_momentum, float second_momentum, float alpha1, float alpha2, float weight_decay,
                       float bias_correction1, float bias_correction2, float clip_lo, float clip_hi,
                       hipStream_t stream);
+int qvit_prune_scores_fold(const void* groups, int ngroups, const void* items, int64_t nitems, const double* sums,
+                           const void* units, int64_t nunits, double* unit_sums, hipStream_t stream);
 int qvit_prune_scores_finish(const void* groups, int ngroups, const void* items, int64_t nitems, const double* sums,
                              double w_magnitude, double w_avg_magnitude, double w_cosine, double w_taylor1,
                              double w_taylor2, float* scores, hipStream_t stream);

@@ -27,7 +27,8 @@ from .calibrate import (
     search_weight_quant,
     set_activation_quant,
 )
-from .qat_optim import PruneGroup, QuantAwareOptimizer, compress_pruned_mlp, vit_mlp_prune_groups
+from .qat_optim import (PruneGroup, QuantAwareOptimizer, compress_pruned_heads, compress_pruned_mlp,
+                        vit_head_prune_groups, vit_mlp_prune_groups)
 
 __all__ = [
     "LAYER_TO_QUANTLAYER", "NanInGradientError", "QuantizationMode", "QuantizationType", "QuantizeConv2d",
@@ -35,4 +36,5 @@ __all__ = [
     "model_to_quantize_model", "QuantChoice", "apply_quant_choices", "build_quantized_vit", "clip_candidates",
     "collect_input_absmax", "quantize_pretrained", "search_activation_quant", "search_weight_quant",
     "set_activation_quant", "QuantAwareOptimizer", "PruneGroup", "vit_mlp_prune_groups", "compress_pruned_mlp",
+    "vit_head_prune_groups", "compress_pruned_heads",
 ]

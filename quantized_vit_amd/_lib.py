@@ -78,6 +78,7 @@ _SIGNATURES = {
     "qvit_qat_step": [_c_p, _i32, _c_p, _i64, _i32, _i32] + [_f32] * 11 + [_c_p],
     "qvit_qat_quant_step": [_c_p, _i32, _c_p, _i32, _i32, _i32, _i32] + [_f32] * 11 + [_i32] * 4 + [_c_p],
     "qvit_prune_scores": [_c_p, _i32, _c_p, _i32, _c_p, _i64, _c_p, _i32, _i32] + [_f32] * 11 + [_c_p],
+    "qvit_prune_scores_fold": [_c_p, _i32, _c_p, _i64, _c_p, _c_p, _i64, _c_p, _c_p],
     "qvit_prune_scores_finish": [_c_p, _i32, _c_p, _i64, _c_p] + [_f64] * 5 + [_c_p, _c_p],
     "qvit_prune_joint_scalars": [_c_p, _i32, _i32, _i32] + [_f32] * 11 + [_i32, _i32, _c_p],
     "qvit_prune_joint_reduce": [_c_p, _i32, _c_p, _i32, _c_p, _i64, _c_p, _i32, _i32] + [_f32] * 11 + [_c_p],
@@ -362,15 +363,25 @@ def qat_quant_step(quants: torch.Tensor, nquants: int, bits: torch.Tensor, stage
 
 
 def prune_scores(groups: torch.Tensor, ngroups: int, members: torch.Tensor, nmembers: int, items: torch.Tensor,
-                 nitems: int, sums: torch.Tensor, weights: tuple, scores: torch.Tensor, hyper: tuple) -> None:
+                 nitems: int, sums: torch.Tensor, weights: tuple, scores: torch.Tensor, hyper: tuple,
+                 units: Optional[torch.Tensor] = None, nunits: int = 0,
+                 unit_sums: Optional[torch.Tensor] = None) -> None:
     """The saliency score of every listed row (qvit_prune_scores, then qvit_prune_scores_finish). `weights`: the five
-    criteria weights in the header's order; `sums` float64 [nitems, 3] and `scores` float32 [nitems] are written."""
+    criteria weights in the header's order; `sums` float64 [nitems, 3] and `scores` float32 [nitems] are written.
+    With `units` (some group's unit is a set of rows) qvit_prune_scores_fold runs between the two: `unit_sums`
+    float64 [nunits, 3] and `scores` float32 [nunits] are written."""
     _require_gpu(groups, "group table")
+    nscores = nitems if units is None else nunits
     assert sums.dtype == torch.float64 and sums.numel() >= 3 * nitems and scores.dtype == torch.float32 and \
-        scores.numel() >= nitems
+        scores.numel() >= nscores
     lib, st = load(), _stream(groups.device)
     _check(lib.qvit_prune_scores(_ptr(groups), ngroups, _ptr(members), nmembers, _ptr(items), nitems, _ptr(sums),
                                  *hyper, st), "qvit_prune_scores")
+    if units is not None:
+        assert unit_sums is not None and unit_sums.dtype == torch.float64 and unit_sums.numel() >= 3 * nunits
+        _check(lib.qvit_prune_scores_fold(_ptr(groups), ngroups, _ptr(items), nitems, _ptr(sums), _ptr(units), nunits,
+                                          _ptr(unit_sums), st), "qvit_prune_scores_fold")
+        items, nitems, sums = units, nunits, unit_sums
     _check(lib.qvit_prune_scores_finish(_ptr(groups), ngroups, _ptr(items), nitems, _ptr(sums),
                                         *[float(w) for w in weights], _ptr(scores), st), "qvit_prune_scores_finish")
 

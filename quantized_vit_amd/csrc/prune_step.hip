@@ -1,7 +1,8 @@
 // The pruning stages of the GETA optimizer for declared row groups (optimizer/geta.py:167-248 period boundary,
 // :281-521 compute_gamma_d, :944-1022 the joint stage; base_hybrid_sparse_optimizer.py:194-211, :221-291;
 // importance_score/*.py), as a fixed number of launches per step whatever the number of groups:
-//   qvit_prune_scores / qvit_prune_scores_finish   the saliency scores of every row of every group (period boundary);
+//   qvit_prune_scores / qvit_prune_scores_finish   the saliency scores of every row of every group (period boundary),
+//   qvit_prune_scores_fold                         between them where a group's unit is a set of rows;
 //   qvit_prune_joint_scalars                       the quantizer scalars of the joint groups' layers;
 //   qvit_prune_joint_reduce / _finish              the six sums of compute_gamma_d, then gamma and d per group;
 //   qvit_prune_joint_apply                         the member tensors' update, moments and row zeroing.
@@ -14,6 +15,12 @@
 // deals items to waves: a wave owns one row of one group across all its members, so a row's sums need no partials
 // and no atomics. A member whose four base pointers are 16-byte aligned and whose width is a multiple of 4 is read
 // and written 16 bytes at a time; any other member one element at a time, by the same per-element function.
+//
+// A group with sections > 1 or unit_rows > 1 prunes units of sections x unit_rows rows: unit h of a member of
+// sections x units x unit_rows rows is the rows (s units + h) unit_rows + j (head h of a qkv projection: sections = 3,
+// unit_rows = the head dim). The rows stay the items and the waves' work, so nothing above changes: the host gives
+// every row its unit's state, lists a redundant unit's rows in the reduce, and only the scores need the unit: one
+// thread per unit folds its rows' three sums in a fixed order (qvit_prune_scores_fold) before the criteria are formed.
 //
 // The gradient variant is recomputed in registers from grad, m and v by qat_common.h's grad_variant, the function
 // the dense step runs, so no grad_variant tensor exists and a member row outside the redundant set gets the bits
@@ -42,15 +49,19 @@ struct PruneGroup {     // 64 B
   int32_t rows;
   int32_t joint;        // 1: the joint stage (active redundant rows); 0: the stage path
   int32_t red_begin, red_count;   // its redundant rows' partials
-  int64_t elems;        // elements per row over all members
-  int64_t reserved;
+  int64_t elems;        // elements per unit over all members
+  int32_t sections, unit_rows;    // 0 as 1; both 1: a unit is one row
 };
 struct PruneItem {      // 16 B
   int32_t group, row;
   int32_t state;        // 0 important, 1 active redundant, 2 pruned
-  int32_t reserved;
+  int32_t link;         // a row item: the row's unit (0 where a unit is one row); a unit entry of the fold (row = the
+                        // unit): the index in the row items of row 0 of its group
 };
 enum { kImportant = 0, kRedundant = 1, kPruned = 2 };
+QVIT_DEV int64_t rows_per_unit(const PruneGroup& G) {
+  return (int64_t)(G.sections > 1 ? G.sections : 1) * (G.unit_rows > 1 ? G.unit_rows : 1);
+}
 
 // the weight quantizer as geta.py:806-850 states it: range_pow has no 1e-6 (the layers' forward has one)
 struct WeightQuant {
@@ -173,6 +184,38 @@ __global__ __launch_bounds__(kThreads) void prune_scores_kernel(const PruneGroup
       sums[3 * i] = pp; sums[3 * i + 1] = gg; sums[3 * i + 2] = pg;
     }
   }
+}
+
+// ---- scores of units of several rows: one thread per unit adds its rows' sums, section-major, row ascending -----------
+__global__ __launch_bounds__(kThreads) void prune_scores_fold_kernel(const PruneGroup* __restrict__ groups, int ngroups,
+                                                                     const PruneItem* __restrict__ items,
+                                                                     int64_t nitems, const double* __restrict__ sums,
+                                                                     const PruneItem* __restrict__ units,
+                                                                     int64_t nunits, double* __restrict__ unit_sums) {
+  const int64_t u = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (u >= nunits) return;
+  const PruneItem un = units[u];
+  double pp = 0.0, gg = 0.0, pg = 0.0;
+  if ((uint32_t)un.group < (uint32_t)ngroups) {
+    const PruneGroup G = groups[un.group];
+    const int64_t S = G.sections > 1 ? G.sections : 1, R = G.unit_rows > 1 ? G.unit_rows : 1;
+    const int64_t count = G.rows > 0 ? G.rows / (S * R) : 0, base = un.link, h = un.row;
+    // the unit and its group's rows lie inside the tables, and the row items are the ones the unit names
+    bool ok = count * S * R == G.rows && h >= 0 && h < count && base >= 0 && base + G.rows <= nitems;
+    for (int64_t s = 0; ok && s < S; ++s)
+      for (int64_t j = 0; j < R; ++j) {
+        const int64_t r = (s * count + h) * R + j;
+        const PruneItem it = items[base + r];
+        if (it.group != un.group || it.row != r || (S * R > 1 && it.link != h)) {
+          ok = false;
+          break;
+        }
+        const double* q = sums + 3 * (base + r);
+        pp += q[0]; gg += q[1]; pg += q[2];
+      }
+    if (!ok) pp = gg = pg = 0.0;
+  }
+  unit_sums[3 * u] = pp; unit_sums[3 * u + 1] = gg; unit_sums[3 * u + 2] = pg;
 }
 
 // the five criteria of one row, in double: magnitude, avg_magnitude, cosine_similarity, taylor first and second order
@@ -360,7 +403,8 @@ __global__ __launch_bounds__(kThreads) void prune_joint_finish_kernel(const Prun
   const double clip_norm = sqrt(s[1]), grad_norm = sqrt(s[2]), res_norm = sqrt(s[4]);
   const double cos_clip = s[0] / (fmax(clip_norm, eps) * grad_norm);
   const double cos_res = s[3] / (fmax(res_norm, eps) * grad_norm);
-  const double mean_clip = s[5] / ((double)G.red_count * (double)G.elems);
+  // red_count rows are red_count / rows_per_unit units of elems elements
+  const double mean_clip = s[5] / ((double)(G.red_count / rows_per_unit(G)) * (double)G.elems);
   const double D = (double)period, tt = (double)t_in_period;
   const double schedule = 1.0 - (D - tt - 1.0) / (D - tt);
   double rate;
@@ -501,6 +545,18 @@ int qvit_prune_scores_finish(const void* groups, int ngroups, const void* items,
   hipLaunchKernelGGL(prune_scores_finish_kernel, dim3(1), dim3(kThreads), 0, stream,
                      static_cast<const PruneGroup*>(groups), ngroups, static_cast<const PruneItem*>(items), nitems,
                      sums, w_magnitude, w_avg_magnitude, w_cosine, w_taylor1, w_taylor2, scores);
+  return qvit_launch_status();
+}
+
+int qvit_prune_scores_fold(const void* groups, int ngroups, const void* items, int64_t nitems, const double* sums,
+                           const void* units, int64_t nunits, double* unit_sums, hipStream_t stream) {
+  if (!groups || !items || !sums || !units || !unit_sums) return QVIT_ENULL;
+  if (qvit_misaligned(7, groups, items, sums, units, unit_sums)) return QVIT_EALIGN;
+  if (ngroups < 0 || nitems < 0 || nitems > INT32_MAX || nunits < 0 || nunits > INT32_MAX) return QVIT_EINVAL;
+  if (ngroups == 0 || nunits == 0) return QVIT_OK;
+  hipLaunchKernelGGL(prune_scores_fold_kernel, dim3((unsigned)cdiv(nunits, kThreads)), dim3(kThreads), 0, stream,
+                     static_cast<const PruneGroup*>(groups), ngroups, static_cast<const PruneItem*>(items), nitems,
+                     sums, static_cast<const PruneItem*>(units), nunits, unit_sums);
   return qvit_launch_status();
 }
 

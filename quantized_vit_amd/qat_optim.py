@@ -7,7 +7,7 @@ two HIP launches (include/qvit_hip.h: qvit_qat_step for every dense tensor, qvit
 scalar and its projection) and no device-to-host copy: the reference makes a few torch launches per parameter and
 reads q_m and t_quant back with .item() per layer, side and step. The pruning stages (saliency scores, redundant
 groups, the joint stage, geta.py:904-1026) run for row groups the user declares (PruneGroup; vit_mlp_prune_groups for
-the MLP hidden units of a ViT): the reference's optimizer takes ready-made parameter groups and only its graph tracer,
+the MLP hidden units of a ViT, vit_head_prune_groups for its attention heads): the reference's optimizer takes ready-made parameter groups and only its graph tracer,
 which is out of scope, produces them. See the second half of this module.
 
 Reference behaviour kept as it is (the trained scalars are the product's input):
@@ -388,7 +388,7 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
         return self._prune
 
     def pruned_rows(self) -> Dict[str, List[int]]:
-        """{group name: sorted rows committed as pruned}."""
+        """{group name: sorted units committed as pruned}: rows of a one-row geometry, heads of a head group."""
         return {g.name: sorted(g.pruned) for g in self._need_prune().groups}
 
     def prune_metrics(self) -> Dict[str, float]:
@@ -407,18 +407,44 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
 # Left out: gl_scale (base_hybrid_sparse_optimizer.py:293-333) is computed by the reference and read by nothing.
 # The one difference: `while d_quant < d_quant_lower` (:494) never ends for d_quant == 0; the device cuts it after 861
 # turns (x 1.25 per turn crosses fp32's exponent range) with d = d_quant_upper and gamma = 0.
-# Out of scope: head and head-dim transforms, TRANSPOSE members, auxiliary groups, LoRA scores, the graph tracer and
-# the verbose log files.
+# Heads: the reference's multihead_numhead_transformation is view(num_groups, -1), which on a [3 dim, dim] qkv weight
+# groups contiguous rows and mixes the q rows of several heads; here a head is what the forward's reshape(B, N, 3, H,
+# hd) makes of it (PruneGroup's sections and unit_rows).
+# Out of scope: head-dim pruning, TRANSPOSE members, auxiliary groups, LoRA scores, the graph tracer and the verbose
+# log files.
 _CRITERIA = ("magnitude", "avg_magnitude", "cosine_similarity", "taylor_first_order", "taylor_second_order")
 
 
 class PruneGroup:
     """One prunable group set: `members` are parameters sliced along dim 0 (the reference's TensorTransform.BASIC),
     all of the same shape[0]; `layer` is the QuantizeLinear whose weight quantizer scalars belong to the group. The
-    layer's weight is the quantized member, every other member (its bias) is unquantized."""
+    layer's weight is the quantized member, every other member (its bias) is unquantized.
 
-    def __init__(self, name: str, layer: nn.Module, members: List[nn.Parameter]):
+    `sections` and `unit_rows` make the prunable unit a set of rows: a member has sections * units * unit_rows rows
+    and unit h is the rows s * units * unit_rows + h * unit_rows + j, s in [0, sections), j in [0, unit_rows). Both 1:
+    unit r is row r. sections = 3, unit_rows = head_dim: head h of a qkv projection as reshape(B, N, 3, H, hd) reads
+    it."""
+
+    def __init__(self, name: str, layer: nn.Module, members: List[nn.Parameter], sections: int = 1,
+                 unit_rows: int = 1):
         self.name, self.layer, self.members = str(name), layer, list(members)
+        self.sections, self.unit_rows = sections, unit_rows
+
+
+def unit_rows_of(units, num_units: int, sections: int = 1, unit_rows: int = 1) -> np.ndarray:
+    """The physical rows of the listed units, unit after unit, each section-major with its rows ascending: the order
+    in which the device folds a unit's sums and the joint stage lists a redundant unit's rows."""
+    h = np.asarray(units, dtype=np.int64).reshape(-1, 1, 1)
+    s = np.arange(sections, dtype=np.int64).reshape(1, -1, 1)
+    j = np.arange(unit_rows, dtype=np.int64).reshape(1, 1, -1)
+    return ((s * num_units + h) * unit_rows + j).reshape(-1)
+
+
+def units_view(p: torch.Tensor, num_units: int, sections: int = 1, unit_rows: int = 1) -> torch.Tensor:
+    """[num_units, elements of a unit] of a member: a view for a one-row geometry, else a permuted copy."""
+    if sections == 1 and unit_rows == 1:
+        return p.reshape(num_units, -1)
+    return p.reshape(sections, num_units, unit_rows, -1).permute(1, 0, 2, 3).reshape(num_units, -1)
 
 
 class _GroupState:
@@ -426,7 +452,10 @@ class _GroupState:
 
     def __init__(self, g: PruneGroup):
         self.name, self.layer, self.members = g.name, g.layer, list(g.members)
-        self.num_groups = int(self.members[0].shape[0])
+        self.sections, self.unit_rows = int(g.sections), int(g.unit_rows)
+        self.rows = int(self.members[0].shape[0])                         # physical rows: the device's items
+        self.num_groups = self.rows // (self.sections * self.unit_rows)   # prunable units
+        self.basic = self.sections == 1 and self.unit_rows == 1
         self.prunable = True
         self.start = 0                      # global index of row 0 among the prunable groups
         self.important: List[int] = list(range(self.num_groups))
@@ -445,6 +474,9 @@ def _check_prune_groups(groups: List[PruneGroup]) -> None:
             raise ValueError(f"group {g.name}: its layer must be a QuantizeLinear with a weight quantizer")
         if not g.members:
             raise ValueError(f"group {g.name} has no members")
+        for what, n in (("sections", g.sections), ("unit_rows", g.unit_rows)):
+            if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 1:
+                raise ValueError(f"group {g.name}: {what} must be an integer >= 1 (got {n!r})")
         for p in g.members:
             if not isinstance(p, torch.Tensor) or p.dim() < 1 or p.dtype != torch.float32:
                 raise ValueError(f"group {g.name}: a member must be a float32 tensor sliced along dim 0 "
@@ -457,6 +489,10 @@ def _check_prune_groups(groups: List[PruneGroup]) -> None:
             seen.add(id(p))
         if len({p.shape[0] for p in g.members}) != 1:
             raise ValueError(f"group {g.name}: members differ in shape[0]: {[tuple(p.shape) for p in g.members]}")
+        per_unit = int(g.sections) * int(g.unit_rows)
+        if g.members[0].shape[0] % per_unit or g.members[0].shape[0] == 0:
+            raise ValueError(f"group {g.name}: shape[0] = {g.members[0].shape[0]} is not sections * units * unit_rows "
+                             f"= {g.sections} * units * {g.unit_rows} for a whole number of units")
 
 
 def vit_mlp_prune_groups(model: nn.Module) -> List[PruneGroup]:
@@ -468,6 +504,19 @@ def vit_mlp_prune_groups(model: nn.Module) -> List[PruneGroup]:
         fc1 = blk.mlp.fc1
         members = [fc1.weight] + ([fc1.bias] if fc1.bias is not None else [])
         groups.append(PruneGroup(f"blocks.{i}.mlp", fc1, members))
+    return groups
+
+
+def vit_head_prune_groups(model: nn.Module) -> List[PruneGroup]:
+    """One PruneGroup per Block: the attention heads, i.e. head h's q, k and v rows of attn.qkv.weight and attn.qkv.bias
+    as the forward's reshape(B, N, 3, H, hd) reads them (sections = 3, unit_rows = head_dim). A zeroed head has
+    q = k = v = 0 exactly, so its output columns are 0 and its activation codes into proj are 0: the matching columns
+    of proj are inert (compress_pruned_heads removes both)."""
+    groups = []
+    for i, blk in enumerate(model.blocks):
+        a = blk.attn
+        members = [a.qkv.weight] + ([a.qkv.bias] if a.qkv.bias is not None else [])
+        groups.append(PruneGroup(f"blocks.{i}.attn", a.qkv, members, sections=3, unit_rows=int(a.head_dim)))
     return groups
 
 
@@ -512,9 +561,50 @@ def refine_by_divisible(g: PruneGroup, group_divisible: int) -> int:
     return delta
 
 
+def prune_tables(groups: List["_GroupState"], order: List[int], folded: bool, grow: np.ndarray) -> dict:
+    """The item tables of the qvit_prune_* entry points from the groups' unit lists, as int64 pairs per 16-byte
+    entry (group | row << 32, state | link << 32), and columns 4 and 5 of the group rows `grow` (rows and joint, the
+    range of the redundant rows), written in place:
+      items  every physical row of every group in `order`, a group's rows ascending, each with its unit's state and,
+             where a unit is several rows, its unit;
+      red    the rows of the active redundant units of the joint groups, a group's rows contiguous, unit after unit in
+             unit_rows_of's order;
+      units  (folded only) one entry per unit of every prunable group: link = the index in items of the group's row 0;
+      joint  the indices of the joint groups, in `order`."""
+    items, red, units, joint_groups = [], [], [], []
+    nitems = nred = 0
+    for gi in order:
+        g = groups[gi]
+        state = np.zeros(g.num_groups, dtype=np.int64)
+        state[g.active] = _lib.PRUNE_REDUNDANT
+        state[g.pruned] = _lib.PRUNE_PRUNED
+        rows = np.arange(g.rows, dtype=np.int64)
+        unit = np.zeros(g.rows, dtype=np.int64) if g.basic else (rows // g.unit_rows) % g.num_groups
+        items.append(np.stack([gi | (rows << 32), (state if g.basic else state[unit]) | (unit << 32)], axis=1))
+        if folded and g.prunable:
+            units.append(np.stack([gi | (np.arange(g.num_groups, dtype=np.int64) << 32), state | (nitems << 32)],
+                                  axis=1))
+        nitems += g.rows
+        joint = g.prunable and len(g.active) > 0
+        grow[gi, 4] = g.rows | (int(joint) << 32)
+        grow[gi, 5] = 0
+        if joint:
+            act = unit_rows_of(g.active, g.num_groups, g.sections, g.unit_rows)
+            link = np.zeros(len(act), np.int64) if g.basic else \
+                np.repeat(np.asarray(g.active, dtype=np.int64), g.sections * g.unit_rows)
+            grow[gi, 5] = nred | (len(act) << 32)
+            red.append(np.stack([gi | (act << 32), _lib.PRUNE_REDUNDANT | (link << 32)], axis=1))
+            nred += len(act)
+            joint_groups.append(gi)
+    empty = np.zeros((0, 2), np.int64)
+    return {"items": np.concatenate(items) if items else empty, "red": np.concatenate(red) if red else empty,
+            "units": np.concatenate(units) if units else empty, "joint": joint_groups}
+
+
 class _PruneState:
     """The pruning half of QuantAwareOptimizer: the host bookkeeping of geta.py:904-919, :1024-1026 and the device
-    tables of the qvit_prune_* entry points. Per step: qvit_prune_joint_apply for the members of every group, and
+    tables of the qvit_prune_* entry points. The host's lists (important, active, pruned, the global ranking) count
+    units; the device's items are physical rows, each with its unit's state. Per step: qvit_prune_joint_apply for the members of every group, and
     while any group has active redundant rows qvit_prune_joint_scalars, _reduce and _finish in front of it; at a
     period boundary qvit_prune_scores and its finish, followed by the step's one host synchronisation."""
 
@@ -569,17 +659,21 @@ class _PruneState:
             elems = 0
             for p in g.members:
                 di = dense_index[id(p)]
-                width = p.numel() // g.num_groups
-                elems += width
+                width = p.numel() // g.rows
+                elems += width * g.sections * g.unit_rows
                 mrows.append([p.data_ptr(), 0, 0 if opt._m[di] is None else opt._m[di].data_ptr(),
                               0 if opt._v[di] is None else opt._v[di].data_ptr(), width,
                               1 if p is ly.weight else 0])
                 self.member_dense.append(di)
                 self.member_group.append(gi)
             self._grow[gi, 6] = elems
+            self._grow[gi, 7] = 0 if g.basic else (g.sections | (g.unit_rows << 32))
         self._mrow = np.array(mrows, dtype=np.int64)
         self.nmembers = len(mrows)
-        self.nrows = sum(g.num_groups for g in groups)
+        self.nrows = sum(g.rows for g in groups)
+        self.nprunable_rows = sum(g.rows for g in groups if g.prunable)
+        # some unit is a set of rows: the scores go through qvit_prune_scores_fold and a table of the units
+        self.folded = any(not g.basic for g in groups if g.prunable)
         self._gtable = _Upload(ng, self._grow.shape[1], dev)
         self._mtable = _Upload(self.nmembers, self._mrow.shape[1], dev)
         self._itable = _Upload(self.nrows, _lib.PRUNE_ITEM_BYTES // 8, dev)    # every row, prunable groups first
@@ -587,6 +681,9 @@ class _PruneState:
         self._jtable = _Upload(2 * ng, opt._qrow.shape[1], dev)
         self._sums = torch.zeros((max(self.nrows, 1), 3), dtype=torch.float64, device=dev)
         self._scores = torch.zeros(max(self.nrows, 1), dtype=torch.float32, device=dev)
+        if self.folded:
+            self._utable = _Upload(self.total_num_groups, _lib.PRUNE_ITEM_BYTES // 8, dev)   # the prunable units
+            self._unit_sums = torch.zeros((max(self.total_num_groups, 1), 3), dtype=torch.float64, device=dev)
         self._partials = torch.zeros((max(self.nrows, 1), 6), dtype=torch.float64, device=dev)
         self.gamma = torch.zeros(ng, dtype=torch.float32, device=dev)
         self.info = torch.full((ng,), -1, dtype=torch.int32, device=dev)
@@ -599,28 +696,13 @@ class _PruneState:
     # ---- tables ---------------------------------------------------------------------------------------------------
     def _tables(self) -> None:
         """The group, item and joint quantizer rows from the host lists (rebuilt when the lists change)."""
-        items, red = [], []
-        self._joint_rows: List[int] = []
-        for gi in self.order:
-            g = self.groups[gi]
-            state = np.zeros(g.num_groups, dtype=np.int64)
-            state[g.active] = _lib.PRUNE_REDUNDANT
-            state[g.pruned] = _lib.PRUNE_PRUNED
-            rows = np.arange(g.num_groups, dtype=np.int64)
-            items.append(np.stack([gi | (rows << 32), state], axis=1))
-            joint = g.prunable and len(g.active) > 0
-            self._grow[gi, 4] = g.num_groups | (int(joint) << 32)
-            begin = sum(len(r) for r in red)
-            self._grow[gi, 5] = (begin | (len(g.active) << 32)) if joint else 0
-            if joint:
-                act = np.asarray(g.active, dtype=np.int64)
-                red.append(np.stack([gi | (act << 32), np.full(len(act), _lib.PRUNE_REDUNDANT, np.int64)], axis=1))
-                self._joint_rows.extend(self.joint_triples[gi])
-        self._items = np.concatenate(items) if items else np.zeros((0, 2), np.int64)
-        self._nred = sum(len(r) for r in red)
+        t = prune_tables(self.groups, self.order, self.folded, self._grow)
+        self._items, self._nred = t["items"], int(t["red"].shape[0])
         self._red = np.zeros((max(self.nrows, 1), 2), dtype=np.int64)
-        if red:
-            self._red[:self._nred] = np.concatenate(red)
+        self._red[:self._nred] = t["red"]
+        if self.folded:
+            self._units = t["units"]
+        self._joint_rows: List[int] = [r for gi in t["joint"] for r in self.joint_triples[gi]]
         self._dirty = True   # the row lists go to the device when they change, not every step
 
     def quant_rows(self, qrow: np.ndarray) -> np.ndarray:
@@ -660,8 +742,13 @@ class _PruneState:
         self._tables()
         self._send()
         ng = len(self.groups)
-        _lib.prune_scores(self._gtable.dev, ng, self._mtable.dev, self.nmembers, self._itable.dev,
-                          self.total_num_groups, self._sums, self.weights, self._scores, hyper)
+        if self.folded:
+            _lib.prune_scores(self._gtable.dev, ng, self._mtable.dev, self.nmembers, self._itable.dev,
+                              self.nprunable_rows, self._sums, self.weights, self._scores, hyper,
+                              units=self._utable.dev, nunits=self.total_num_groups, unit_sums=self._unit_sums)
+        else:
+            _lib.prune_scores(self._gtable.dev, ng, self._mtable.dev, self.nmembers, self._itable.dev,
+                              self.total_num_groups, self._sums, self.weights, self._scores, hyper)
         chosen = select_redundant(self._scores[:self.total_num_groups], self.taken, self.per_period[self.curr_period])
         self.taken.extend(chosen)
         for g in self.groups:
@@ -678,6 +765,8 @@ class _PruneState:
             self._gtable.send(self._grow)
             self._itable.send(self._items)
             self._rtable.send(self._red)
+            if self.folded:
+                self._utable.send(self._units)
             self._dirty = False
 
     def finish_step(self, n: int, hyper: tuple) -> None:
@@ -728,7 +817,8 @@ class _PruneState:
         for g in self.groups:
             if not g.prunable:
                 continue
-            sq = sum(p.detach().reshape(g.num_groups, -1).double().pow(2).sum(dim=1) for p in g.members)
+            sq = sum(units_view(p.detach(), g.num_groups, g.sections, g.unit_rows).double().pow(2).sum(dim=1)
+                     for p in g.members)
             norm = sq.sqrt().cpu().numpy()
             red = g.active + g.pruned
             m["num_zero_groups"] += int(np.sum(norm == 0))
@@ -786,4 +876,35 @@ def compress_pruned_mlp(model: nn.Module) -> nn.Module:
             raise ValueError("compress_pruned_mlp: a block's MLP has no hidden unit left")
         blk.mlp.fc1 = _resized_linear(fc1, fc1.weight[keep], None if fc1.bias is None else fc1.bias[keep])
         blk.mlp.fc2 = _resized_linear(fc2, fc2.weight[:, keep], fc2.bias)
+    return model
+
+
+@torch.no_grad()
+def compress_pruned_heads(model: nn.Module) -> nn.Module:
+    """Removes every attention head whose q, k and v rows of attn.qkv.weight and entries of attn.qkv.bias are all
+    zero, together with the matching columns of attn.proj.weight, in place, and returns the model; sets
+    attn.num_heads and leaves head_dim and the softmax scale as they are. The quantizer scalars are carried over and
+    the plans start afresh. A removed head's bias entries are zero, so the qkv layer's output bound, and with it the
+    attention input scale, is the uncompressed layer's. Composes with compress_pruned_mlp in either order. An
+    optimizer built over the model before the call no longer matches it."""
+    for blk in model.blocks:
+        a = blk.attn
+        H, hd = int(a.num_heads), int(a.head_dim)
+        if a.qkv.out_features != 3 * H * hd or a.proj.in_features != H * hd:
+            raise ValueError(f"compress_pruned_heads: qkv has {a.qkv.out_features} outputs and proj {a.proj.in_features} "
+                             f"inputs, not 3 x {H} x {hd} and {H} x {hd}")
+        dead = (units_view(a.qkv.weight, H, 3, hd) == 0).all(dim=1)
+        if a.qkv.bias is not None:
+            dead &= (units_view(a.qkv.bias, H, 3, hd) == 0).all(dim=1)
+        keep = (~dead).nonzero().flatten().tolist()
+        if len(keep) == H:
+            continue
+        if not keep:
+            raise ValueError("compress_pruned_heads: a block's attention has no head left")
+        rows = torch.from_numpy(unit_rows_of(keep, H, 3, hd).reshape(len(keep), 3, hd).transpose(1, 0, 2).reshape(-1)
+                                ).to(a.qkv.weight.device)   # section-major again: [3, kept heads, hd]
+        cols = torch.from_numpy(unit_rows_of(keep, H, 1, hd)).to(a.qkv.weight.device)
+        a.qkv = _resized_linear(a.qkv, a.qkv.weight[rows], None if a.qkv.bias is None else a.qkv.bias[rows])
+        a.proj = _resized_linear(a.proj, a.proj.weight[:, cols], a.proj.bias)
+        a.num_heads = len(keep)
     return model
