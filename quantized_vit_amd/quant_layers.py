@@ -288,9 +288,78 @@ def _conv_backward_gemm_ops(overlap: bool) -> tuple:
         raise ValueError(f"CONV_BACKWARD_GEMM = {CONV_BACKWARD_GEMM!r}: expected hip, torch, dgrad or wgrad") from None
 
 
+def _wreg_unit_order(device: torch.device) -> torch.Tensor:
+    """For each of the 1024 fragments of a (tile_n, k-stage) chunk of a register image, in the image's order, the
+    index of the 8-byte fragment of the packed W4 chunk it was taken from (pack_w4r_kernel / pack_w8r_kernel: wave w,
+    lane l, r -> row 64 w + 16 r + (l & 15), the row's k-chunk (l >> 4) ^ (2 if l & 8 else 0)): a permutation."""
+    u = torch.arange(1024, device=device)
+    w, ln, r = (u >> 8) & 3, (u >> 2) & 63, u & 3
+    lfr, lfq = ln & 15, ln >> 4
+    return (64 * w + 16 * r + lfr) * 4 + (lfq ^ (((lfr >> 3) & 1) << 1))
+
+
+def unpack_wreg(image: torch.Tensor, wfmt: int, npad: int, kpad: int) -> torch.Tensor:
+    """The packed W4 codes (qvit_pack_weight layout) a register image was made from, bit for bit: the inverse of
+    qvit_pack_weight_w4r (a permutation of 8-byte fragments) or qvit_pack_weight_w8r (the same permutation, every
+    nibble widened to the byte 16 k). Torch index ops on the device: this runs once per plan and route, never per
+    forward."""
+    if wfmt == _lib.W8R:
+        q = image.view(torch.int32).view(-1, 4)   # nib16_lo(p.x), nib16_hi(p.x), nib16_lo(p.y), nib16_hi(p.y)
+        lo, hi = 0x0F0F0F0F, -0x0F0F0F10            # 0xF0F0F0F0 as an int32
+        frags = torch.stack([((q[:, 0] >> 4) & lo) | (q[:, 1] & hi), ((q[:, 2] >> 4) & lo) | (q[:, 3] & hi)], 1)
+    elif wfmt == _lib.W4R:
+        frags = image.view(torch.int32).view(-1, 2)
+    else:
+        raise ValueError(f"unpack_wreg: wfmt {wfmt} is no register image")
+    frags = frags.view(-1, 1024, 2)
+    out = torch.empty_like(frags)
+    out[:, _wreg_unit_order(image.device)] = frags
+    packed = out.view(-1).view(torch.uint8)
+    assert packed.numel() == npad * kpad // 2
+    return packed
+
+
+def unpack_codes(packed: torch.Tensor, wfmt: int, npad: int, kpad: int) -> torch.Tensor:
+    """The integer codes of a packed weight image, fp32 [npad, kpad]: the inverse of qvit_pack_weight's layout
+    (quant_kernels.hip: packed_offset, perm_row) in torch index ops, exact. Per (256-row block, 64-k stage) tile, row
+    r holds its 16-k chunk c at position c ^ (2 if r & 8 else 0) (W4, 8 bytes: byte b of each half = codes b and
+    b + 4 as low and high nibble) or c ^ (2 if r & 4 else 0) (W8, 16 bytes); packed row rho is weight row rho with
+    bits [3:2] and [5:4] swapped; W16 / W24 are two / three W8 images of base-256 digits, most significant first."""
+    dev = packed.device
+    if wfmt in (_lib.W16, _lib.W24):
+        digits = packed.view(-1, npad * kpad)
+        out = torch.zeros((npad, kpad), dtype=torch.float32, device=dev)
+        for img in digits:     # exact in fp32: |codes| < 2^23
+            out = out * 256.0 + unpack_codes(img, _lib.W8, npad, kpad)
+        return out
+    nb, st = npad // 256, kpad // 64
+    r = torch.arange(256, device=dev)
+    pos = torch.arange(4, device=dev)
+    if wfmt == _lib.W4:
+        b = packed.view(nb, st, 256, 4, 2, 4).to(torch.int16)
+        nib = torch.stack([b & 15, b >> 4], dim=-2)                  # [..., half, low / high nibble, byte]
+        vals = ((nib ^ 8) - 8).reshape(nb, st, 256, 4, 16)           # sign-extended, k order within the chunk
+        swz = ((r >> 3) & 1) << 1
+    elif wfmt == _lib.W8:
+        vals = packed.view(torch.int8).view(nb, st, 256, 4, 16).to(torch.int16)
+        swz = ((r >> 2) & 1) << 1
+    else:
+        raise ValueError(f"unpack_codes: wfmt {wfmt}")
+    chunk_at = pos[None, :] ^ swz[:, None]                            # [row, chunk] -> position
+    vals = vals.gather(3, chunk_at[None, None, :, :, None].expand(nb, st, 256, 4, 16))
+    rows = vals.permute(0, 2, 1, 3, 4).reshape(npad, kpad)            # packed rows x k
+    rho = torch.arange(npad, device=dev)
+    perm = (rho & ~63) | (((rho >> 2) & 3) << 4) | (((rho >> 4) & 3) << 2) | (rho & 3)   # an involution
+    return rows[perm].float()
+
+
 @dataclass
 class QuantPlan:
-    """Per-layer device state derived from the parameters (rebuilt when any of them changes)."""
+    """Per-layer device state derived from the parameters (rebuilt when any of them changes). Every image the plan
+    hands out, also one it builds later, is made from what the plan holds (the packed codes or the register image,
+    its copies of the bias and its views of the quantizer scalars), never from the layer's live weight: after an
+    edit the key cannot see (`.data`), the plan answers for the weights it was built from on every route until
+    invalidate()."""
     key: tuple
     device: torch.device
     qtype: int
@@ -312,35 +381,78 @@ class QuantPlan:
     qm_act: Optional[torch.Tensor] = None
     t_act: Optional[torch.Tensor] = None
     extra: dict = field(default_factory=dict)
+    # views of every tensor the key names by address: while the plan lives their storage cannot be freed and handed
+    # to a new parameter, so an equal key always means the same tensors
+    held: tuple = ()
+
+    @property
+    def has_codes(self) -> bool:
+        """The plan holds packed weight codes (integer path or weight-only GEMM), so packed_t() can transpose them."""
+        return self.int_path or bool(self.extra.get("wonly"))
+
+    def __deepcopy__(self, memo):
+        # a copied layer has parameters at other addresses: it builds its own plan (and copies no device images)
+        return None
 
     def gemm_weights(self) -> Tuple[torch.Tensor, int]:
         """(image, wfmt) the int path's GEMM reads: the register image (W4R / W8R) of a W4 plan, else the packed
         codes. The register image is built on the first call and the packed codes it is made from are then
-        released, so a layer holds its int4 weights once (conv layers and the fused qkv + attention kernel never
-        call this and keep only the packed codes); `packed_codes()` re-packs them for a route that needs them."""
+        released, so a layer holds its int4 weights once. Every int-path layer comes through here (QuantizeLinear,
+        and QuantizeConv2d by conv_codes_gemm -> gemm_codes); the fused qkv + attention kernel, the residual GEMM
+        with LayerNorm and the weight-stationary fc1 GEMM read the packed codes, which `packed_codes()` gives
+        back."""
         if self.int_path and self.wfmt == _lib.W4 and GEMM_WREG != "w4" and "wreg" not in self.extra:
             src = self.packed_codes()
             pack = _lib.pack_weight_w4r if GEMM_WREG == "w4r" else _lib.pack_weight_w8r
-            self.extra["wreg"] = (pack(src, self.npad, self.kpad), _lib.W4R if GEMM_WREG == "w4r" else _lib.W8R)
-            if self.extra.get("repack") is not None:
-                self.packed = None
+            image, fmt = pack(src, self.npad, self.kpad), _lib.W4R if GEMM_WREG == "w4r" else _lib.W8R
+            self.extra["wreg"] = (image, fmt)
+            # how the packed codes come back: un-permuted from the register image (the closure holds that image,
+            # not the layer's weights)
+            npad, kpad = self.npad, self.kpad
+            self.extra["repack"] = lambda: unpack_wreg(image, fmt, npad, kpad)
+            self.packed = None
         wreg = self.extra.get("wreg")
         return wreg if wreg is not None else (self.packed_codes(), self.wfmt)
 
     def packed_codes(self) -> torch.Tensor:
-        """The packed weight codes (qvit_pack_weight layout), re-packed from the layer's weights if
-        gemm_weights() released them (the same call that made them: deterministic, no overflow to re-check)."""
+        """The packed weight codes (qvit_pack_weight layout); if gemm_weights() released them, un-permuted from
+        the register image it kept (unpack_wreg: the same bytes) and held from then on."""
         if self.packed is None:
             self.packed = self.extra["repack"]()
         return self.packed
 
+    def codes(self) -> torch.Tensor:
+        """The plan's integer weight codes, fp32 [n, k], read back from the packed image it holds (unpack_codes).
+        Serves the images built after the plan (packed_t, w_fakequant, weight_codes), so they hold the codes of the
+        forward whatever became of the layer's weight."""
+        if not self.has_codes:
+            raise _lib.QvitError("QuantPlan.codes: the plan holds no packed codes")
+        packed = self.packed if self.packed is not None else self.extra["repack"]()   # a released image: not kept
+        return unpack_codes(packed, self.wfmt, self.npad, self.kpad)[:self.n, :self.k]
+
     def packed_t(self) -> Tuple[torch.Tensor, int, int]:
         """(image, npad, kpad) of the TRANSPOSED weight codes in the plan's wfmt (rows = in-features padded to
         TILE_N, reduction = out-features padded to TILE_K): the operand of the input gradient on qvit_gemm_wonly.
-        Packed on the first backward and kept with the plan (whose key follows every parameter update)."""
+        Packed from codes() on the first backward and kept with the plan (whose key follows every parameter
+        update); packing integers with the linear quantizer at d = 1 reproduces them exactly."""
         if "packed_t" not in self.extra:
             npad_t, kpad_t = _round_up(self.k, _lib.TILE_N), _round_up(self.n, _lib.TILE_K)
-            self.extra["packed_t"] = (self.extra["pack_t"](npad_t, kpad_t), npad_t, kpad_t)
+            if "t_src" in self.extra:   # a training-mode plan: the weight of this very step (_build_plan)
+                src, qargs = self.extra["t_src"]
+                overflow = torch.zeros(1, dtype=torch.int32, device=self.device)
+                image = _lib.pack_weight(src.t().contiguous(), *qargs, self.wfmt, npad_t, kpad_t, overflow)
+                self.extra["packed_t"] = (image, npad_t, kpad_t)
+                return self.extra["packed_t"]
+            ct = self.codes().t().contiguous()
+            if self.wfmt in (_lib.W16, _lib.W24):   # the same largest code: the same digit count
+                image, wfmt = _lib.pack_weight_wide(ct, npad_t, kpad_t)
+                assert wfmt == self.wfmt
+            else:
+                overflow = torch.zeros(1, dtype=torch.int32, device=self.device)
+                image = _lib.pack_weight(ct, _lib.QT_LINEAR, torch.ones(1, device=self.device),
+                                         torch.full((1,), 1024.0, device=self.device), None, self.wfmt, npad_t,
+                                         kpad_t, overflow)
+            self.extra["packed_t"] = (image, npad_t, kpad_t)
         return self.extra["packed_t"]
 
 
@@ -463,7 +575,7 @@ class QuantizeMixin:
             if tuple(c.shape) != tuple(self.weight.shape):
                 raise ValueError(f"weight codes of shape {tuple(c.shape)} for a weight of shape "
                                  f"{tuple(self.weight.shape)}")
-            self._weight_codes = (self._plan_key(), c.reshape(c.shape[0], -1).to(torch.int16))
+            self._weight_codes = (self._plan_key(), c.reshape(c.shape[0], -1).to(torch.int16), self._held_tensors())
         self._qplan = None
 
     def _bound_weight_codes(self, key: tuple) -> Optional[torch.Tensor]:
@@ -478,6 +590,11 @@ class QuantizeMixin:
     def _quant_param_tensors(self):
         names = ["weight", "bias", "d_quant_wt", "q_m_wt", "t_quant_wt", "d_quant_act", "q_m_act", "t_quant_act"]
         return [getattr(self, n, None) for n in names]
+
+    def _held_tensors(self) -> tuple:
+        """A view of every tensor _plan_key names by address, for whoever keeps such a key: the storage stays
+        allocated, so no later parameter can take the address at the same version."""
+        return tuple(None if p is None else p.detach() for p in self._quant_param_tensors())
 
     def _plan_key(self) -> tuple:
         key = [self.quant_type, self.quant_mode, self.training]
@@ -528,7 +645,7 @@ class QuantizeMixin:
         la = saturation_level(qt, s[3], s[4], s[5] if t_act is not None else 1.0) if wa else float("inf")
         plan = QuantPlan(key=key, device=dev, qtype=qt, n=n, k=k, npad=npad, kpad=kpad, wfmt=0, int_path=False,
                          level_wt=lw, level_act=la, d_wt=d_wt, qm_wt=qm_wt, t_wt=t_wt, d_act=d_act,
-                         qm_act=qm_act, t_act=t_act)
+                         qm_act=qm_act, t_act=t_act, held=self._held_tensors())
         w32 = w2 if (w2.dtype == torch.float32 and w2.is_contiguous()) else w2.float().contiguous()
         act_ok = wa and abs(la) <= 127
         codes = self._bound_weight_codes(key)
@@ -551,10 +668,6 @@ class QuantizeMixin:
                 packed = _lib.pack_weight(w32, qt_pack, d_pack, qm_pack, t_pack, wfmt, npad, kpad, overflow)
                 if int(overflow.item()) == 0:
                     plan.packed, plan.wfmt, plan.int_path = packed, wfmt, True
-                    plan.extra["pack_t"] = self._packer_t(w2, codes, (qt_pack, d_pack, qm_pack, t_pack), wfmt)
-                    if wfmt == _lib.W4:   # how gemm_weights() gets the packed codes back after releasing them
-                        plan.extra["repack"] = self._repacker(w2, codes, (qt_pack, d_pack, qm_pack, t_pack),
-                                                              wfmt, npad, kpad)
                     break
         if not plan.int_path and abs(lw) <= 65536:
             # fp32 activations against the packed weight codes (qvit_gemm_wonly, QuantizeLinear): the weight-only
@@ -569,15 +682,18 @@ class QuantizeMixin:
                     if int(overflow.item()) == 0:
                         plan.packed, plan.wfmt = packed, wfmt
                         plan.extra["wonly"] = True
-                        plan.extra["pack_t"] = self._packer_t(w2, codes, (qt_pack, d_pack, qm_pack, t_pack), wfmt)
                         break
             else:
                 wc = codes.to(device=dev, dtype=torch.float32) if codes is not None else \
                     (_lib.fake_quant_f32(w32, qt, d_wt, qm_wt, t_wt) / d_wt).round()
                 plan.packed, plan.wfmt = _lib.pack_weight_wide(wc, npad, kpad)
                 plan.extra["wonly"] = True
-                plan.extra["pack_t"] = self._packer_t(w2, codes, (qt, d_wt, qm_wt, t_wt), 0)
-        if plan.int_path or plan.extra.get("wonly"):
+        if self.training and plan.wfmt in (_lib.W4, _lib.W8):
+            # a training-mode plan is rebuilt on every call, so the weight it was built from is the live one for the
+            # whole step: its backward packs the transposed codes straight from that weight (one transposing copy and
+            # one pack kernel per step and layer, as before the plan learnt to decode its own image)
+            plan.extra["t_src"] = (w32, (qt_pack, d_pack, qm_pack, t_pack))
+        if plan.has_codes:
             bias = self.bias.detach() if self.bias is not None else None
             plan.bias_pad = _lib.pad_bias(bias, n, npad, dev)
             # |output| <= d_act d_wt sum_k |a_k||w_k| + |bias| <= d_act d_wt K L_a L_w + max|bias| (integer path
@@ -586,46 +702,21 @@ class QuantizeMixin:
                 else float("inf")
         if wa:   # host copies of the activation quantizer's scalars (epilogue code tables of the producer)
             plan.extra["act_host"] = (qt, s[3], s[4], s[5] if t_act is not None else 1.0, la)
-        if not plan.int_path and not plan.extra.get("wonly"):   # levels that fit neither int4 nor int8 (e.g. 16/32
-            plan.w_fakequant = self._fake_quant_weight(plan)     # bits); the fp32 form is otherwise filled lazily
+        # the fp32 form, where the forward itself contracts it: levels that fit no packed format (beyond 65536), and
+        # a convolution the code kernels do not take (groups, padding modes); otherwise it is filled lazily, from
+        # the plan's codes (w_fakequant)
+        if (not plan.int_path and not plan.extra.get("wonly")) or not self._codes_forward_ok():
+            plan.w_fakequant = self._fake_quant_weight(plan)
         return plan
 
-    @staticmethod
-    def _repacker(w2: torch.Tensor, codes: Optional[torch.Tensor], qargs: tuple, wfmt: int, npad: int, kpad: int):
-        """A closure that repeats quant_plan's packing of these weights (the fp32 source is re-derived on the call,
-        so the plan holds no fp32 copy)."""
-        def repack() -> torch.Tensor:
-            if codes is not None:
-                src = codes.to(device=w2.device, dtype=torch.float32).contiguous()
-            else:
-                src = w2 if (w2.dtype == torch.float32 and w2.is_contiguous()) else w2.float().contiguous()
-            overflow = torch.zeros(1, dtype=torch.int32, device=w2.device)
-            return _lib.pack_weight(src, *qargs, wfmt, npad, kpad, overflow)
-        return repack
-
-    @staticmethod
-    def _packer_t(w2: torch.Tensor, codes: Optional[torch.Tensor], qargs: tuple, wfmt: int):
-        """A closure that packs the transposed weight codes (QuantPlan.packed_t). The quantizers are elementwise, so
-        packing the transposed fp32 weight (or the transposed bound codes) gives exactly the forward's codes;
-        wfmt 0: wide codes as base-256 digits (pack_weight_wide picks W16 / W24 from the same largest code)."""
-        def pack(npad_t: int, kpad_t: int) -> torch.Tensor:
-            if codes is not None:
-                src = codes.to(device=w2.device, dtype=torch.float32)
-            else:
-                src = w2.float()
-            if wfmt == 0:
-                if codes is None:
-                    qt, d, qm, t = qargs
-                    src = (_lib.fake_quant_f32(src.contiguous(), qt, d, qm, t) / d).round()
-                return _lib.pack_weight_wide(src.t().contiguous(), npad_t, kpad_t)[0]
-            overflow = torch.zeros(1, dtype=torch.int32, device=w2.device)
-            return _lib.pack_weight(src.t().contiguous(), *qargs, wfmt, npad_t, kpad_t, overflow)
-        return pack
+    def _codes_forward_ok(self) -> bool:
+        """Whether the forward of a plan with packed codes runs on them (QuantizeConv2d: _int_conv_ok)."""
+        return True
 
     def _fake_quant_weight(self, plan: QuantPlan) -> torch.Tensor:
-        """quantize_weight(W) on the device; with codes bound by load_weight_codes, d_w * k of exactly those
-        codes (also when the plan is on the int path and the fp32 form is only filled later, e.g. for a
-        grouped conv whose forward takes the library path)."""
+        """quantize_weight(W) on the device, from the layer's weight: only while the plan is being built (the
+        weight is then the one the key names); with codes bound by load_weight_codes, d_w * k of exactly those
+        codes."""
         codes = self._bound_weight_codes(plan.key)
         if codes is not None:
             k = codes.to(device=plan.device, dtype=torch.float32)
@@ -639,12 +730,9 @@ class QuantizeMixin:
         wc = self._bound_weight_codes(plan.key)
         if wc is not None:
             return wc.to(device=plan.device, dtype=torch.float32)
-        w = self._weight_2d().float().contiguous()
-        if abs(plan.level_wt) > 127:
-            return (_lib.fake_quant_f32(w, plan.qtype, plan.d_wt, plan.qm_wt, plan.t_wt) / plan.d_wt).round()
-        codes = torch.empty((w.shape[0], plan.kpad), dtype=torch.int8, device=plan.device)
-        _lib.quantize_act_i8(w, plan.qtype, plan.d_wt, plan.qm_wt, plan.t_wt, 0, codes, plan.kpad)
-        return codes[:, :w.shape[1]].float()
+        if plan.int_path or plan.extra.get("wonly"):
+            return plan.codes().contiguous()       # what the plan's kernels multiply by
+        return (plan.w_fakequant.reshape(plan.n, plan.k) / plan.d_wt).round()
 
     def _wonly_rows(self, x2: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
         """[M, k] fp32 rows (or rows already zero-padded to kpad columns) @ quantize_weight(W)^T + b on
@@ -661,9 +749,13 @@ class QuantizeMixin:
         return y if ldy == plan.n else y[:, :plan.n]
 
     def w_fakequant(self, plan: QuantPlan) -> torch.Tensor:
-        """The reference's quantize_weight(W) (quant_layers.py:332-354), cached on the plan."""
+        """The reference's quantize_weight(W) (quant_layers.py:332-354), cached on the plan: d_w * k of the plan's
+        own codes (qvit_fake_quant_f32's value, fake_quant_value in qvit_common.h, for every finite weight up to the
+        sign of zero: a negative weight with code 0 gives +0.0 here and -0.0 there, which no contraction with finite
+        operands can tell apart; a NaN weight has the code 0 the kernels contract, where qvit_fake_quant_f32 passes
+        the NaN on)."""
         if plan.w_fakequant is None:
-            plan.w_fakequant = self._fake_quant_weight(plan)
+            plan.w_fakequant = (plan.d_wt * plan.codes()).view(self.weight.shape)
         return plan.w_fakequant
 
     def _check_input(self, x: torch.Tensor) -> None:
@@ -980,7 +1072,7 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
     def _backward_gemm_routes(self, plan, need_xq, need_wq):
         ops = _backward_gemm_ops()
         has_codes = plan.int_path or bool(plan.extra.get("wonly"))
-        return (need_xq and "dgrad" in ops and has_codes and "pack_t" in plan.extra,
+        return (need_xq and "dgrad" in ops and has_codes,
                 need_wq and "wgrad" in ops and plan.int_path)
 
     def _gemm_grads_hip(self, plan, xf, x_q, w_q, G, hip_x, hip_w):
@@ -1070,7 +1162,7 @@ def _preop_plan(layer) -> Optional[QuantPlan]:
     if set(_backward_gemm_ops()) != {"dgrad", "wgrad"}:
         return None
     plan = layer.quant_plan()
-    return plan if plan.int_path and "pack_t" in plan.extra and plan.k % 4 == 0 else None
+    return plan if plan.int_path and plan.k % 4 == 0 else None
 
 
 class _PreOpLinearFunction(torch.autograd.Function):
@@ -1169,6 +1261,8 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
 
     def _int_conv_ok(self) -> bool:
         return (self.groups == 1 and self.padding_mode == "zeros" and not isinstance(self.padding, str))
+
+    _codes_forward_ok = _int_conv_ok
 
     # -- uint8 image input: ToTensor + Normalize (predict.py:18-19) and quantize_act as tables of 256 entries --------
     def set_uint8_input(self, mean, std) -> None:
@@ -1284,7 +1378,7 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
 
     def _backward_gemm_routes(self, plan, need_xq, need_wq):
         ops = _conv_backward_gemm_ops(self._taps_overlap())
-        if not self._int_conv_ok() or "pack_t" not in plan.extra:
+        if not self._int_conv_ok() or not plan.has_codes:
             return False, False   # groups, padding modes and levels the kernels do not take: the library, as before
         has_codes = plan.int_path or bool(plan.extra.get("wonly"))
         return need_xq and "dgrad" in ops and has_codes, need_wq and "wgrad" in ops and plan.int_path

@@ -293,6 +293,9 @@ class _PackedCodes:
         self.d_wt = torch.full((1,), 1.0 / n_lvl, dtype=torch.float32, device=dev)
         self.bias_pad = _lib.pad_bias(bias, cout, self.npad, dev)
         self._shape4, self._w_bit, self._packed_t = (cout, cin, kh, kw), w_bit, None
+        # views of the tensors the key names by address: their storage stays allocated while the key is kept, so a
+        # replaced parameter cannot take the address (and the key) of the one these codes were made from
+        self._held = (weight.detach(), None if bias is None else bias.detach())
         self.key = key
         return self
 
@@ -494,10 +497,14 @@ def conv2d_Q_fn(w_bit):
                     and not _needs_grad(self, input) and not _needs_grad(bn, input)):
                 return None
             c = self._codes.get(self.weight, self.bias, self.w_bit)
-            key = tuple((t.data_ptr(), t._version) for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var)
-                        if t is not None) + (bn.eps, input.device)
+            # num_batches_tracked stands for the running statistics: a library batch norm updates those through raw
+            # pointers (no version bump), the module's own counter increment is always seen
+            tensors = [t for t in (bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked)
+                       if t is not None]
+            key = tuple((t.data_ptr(), t._version) for t in tensors) + (bn.eps, input.device)
             if self._bn_fold is None or self._bn_fold[0] != key:
-                self._bn_fold = (key, *_lib.ultra_bn_fold(bn, input.device))
+                # (key, alpha, shift, views that keep the addresses in the key from being reused)
+                self._bn_fold = (key, *_lib.ultra_bn_fold(bn, input.device), tuple(t.detach() for t in tensors))
             return _lib.conv_wonly_bn_act(input.detach(), self.kernel_size, self.stride, self.padding, self.dilation,
                                           c.packed, c.wfmt, c.n, c.npad, c.kpad, c.d_wt, c.bias_pad, self._bn_fold[1],
                                           self._bn_fold[2], 2 ** act.a_bit - 1)

@@ -125,6 +125,7 @@ class UltraNetQua(nn.Module):
         self.yolo_layers = [self.yololayer]
         self._plan = None
         self._plan_key = None
+        self._plan_held = None
 
     # ---- fused path ---------------------------------------------------------------------------
     def _blocks(self):
@@ -181,6 +182,8 @@ class UltraNetQua(nn.Module):
         key = self._key()
         if self._plan is None or self._plan_key != key:
             self._plan, self._plan_key = self._build_plan(x.device), key
+            # views of the tensors the key names by address: none of them can be freed and its address reused
+            self._plan_held = [t.detach() for t in list(self.parameters()) + list(self.buffers())]
         plan, (hcodes, hbias, hout) = self._plan
         img_size = x.shape[-2:]
         c0, a0, s0, _, _ = plan[0]

@@ -43,7 +43,7 @@ def make_layer(dev, cin, cout, k, s, p):
         layer.d_quant_act.fill_(3.0 / 127.3)       # levels 127: int8 activation codes
     layer.invalidate()
     plan = layer.quant_plan()
-    assert plan.int_path and plan.wfmt == _lib.W4 and "pack_t" in plan.extra
+    assert plan.int_path and plan.wfmt == _lib.W4 and plan.has_codes
     return layer, plan
 
 
