@@ -27,8 +27,9 @@ from .calibrate import (
     search_weight_quant,
     set_activation_quant,
 )
-from .qat_optim import (PruneGroup, QuantAwareOptimizer, compress_pruned_heads, compress_pruned_mlp,
-                        vit_head_prune_groups, vit_mlp_prune_groups)
+from .qat_optim import QuantAwareOptimizer
+from .qat_prune import PruneGroup, vit_head_prune_groups, vit_mlp_prune_groups
+from .compress import compress_pruned_heads, compress_pruned_mlp
 
 __all__ = [
     "LAYER_TO_QUANTLAYER", "NanInGradientError", "QuantizationMode", "QuantizationType", "QuantizeConv2d",

@@ -9,8 +9,9 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from typing import Optional, Tuple
+from typing import NamedTuple, Optional, Tuple
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -55,6 +56,42 @@ PRUNE_GROUP_BYTES = 64    # the group, member and item descriptors of the qvit_p
 PRUNE_MEMBER_BYTES = 48
 PRUNE_ITEM_BYTES = 16
 PRUNE_IMPORTANT, PRUNE_REDUNDANT, PRUNE_PRUNED = 0, 1, 2
+
+# The descriptors as numpy dtypes: the Python statement of the structs' layouts (their fields, in their order; natural
+# alignment leaves no padding). The host tables are arrays of these and reach the device byte for byte.
+_P, _I = "<i8", "<i4"   # a device pointer or int64_t, an int32_t
+QAT_TENSOR_DTYPE = np.dtype([("p", _P), ("grad", _P), ("m", _P), ("v", _P), ("numel", _P), ("lr_class", _I),
+                             ("flags", _I)])
+QAT_CHUNK_DTYPE = np.dtype([("tensor", _I), ("index", _I)])
+QAT_QUANT_DTYPE = np.dtype([("s", _P, (3,)), ("g", _P, (3,)), ("mom", _P), ("side", _I), ("flags", _I)])
+PRUNE_GROUP_DTYPE = np.dtype([("d", _P), ("qm", _P), ("t", _P), ("member_begin", _I), ("member_count", _I),
+                              ("rows", _I), ("joint", _I), ("red_begin", _I), ("red_count", _I), ("elems", _P),
+                              ("sections", _I), ("unit_rows", _I)])
+PRUNE_MEMBER_DTYPE = np.dtype([("p", _P), ("grad", _P), ("m", _P), ("v", _P), ("width", _P), ("quantized", _I),
+                               ("flags", _I)])
+PRUNE_ITEM_DTYPE = np.dtype([("group", _I), ("row", _I), ("state", _I), ("link", _I)])
+for _dt, _n in ((QAT_TENSOR_DTYPE, QAT_TENSOR_BYTES), (QAT_CHUNK_DTYPE, 8), (QAT_QUANT_DTYPE, QAT_QUANT_BYTES),
+                (PRUNE_GROUP_DTYPE, PRUNE_GROUP_BYTES), (PRUNE_MEMBER_DTYPE, PRUNE_MEMBER_BYTES),
+                (PRUNE_ITEM_DTYPE, PRUNE_ITEM_BYTES)):
+    assert _dt.itemsize == _n, (_dt, _n)
+
+
+class Hyper(NamedTuple):
+    """The hyper-parameters of one step, in the order the qvit_qat_* and qvit_prune_* entry points take them."""
+    variant: int
+    first_step: int
+    lr: float
+    lr_quant: float
+    first_momentum: float
+    second_momentum: float
+    alpha1: float
+    alpha2: float
+    weight_decay: float
+    bias_correction1: float
+    bias_correction2: float
+    clip_lo: float
+    clip_hi: float
+
 
 U8_NCHW = 0
 U8_NHWC = 1

@@ -77,7 +77,7 @@ def test_unit_scores_against_float64(dev, variant, later):
         p = torch.cat([before_u[m].reshape(gr.num_groups, -1) for m in gr.members], dim=1).double().numpy()
         gv = np.concatenate([gv_u[m].reshape(gr.num_groups, -1) for m in gr.members], axis=1).astype(np.float64)
         n = p.shape[1]
-        assert n == int(opt._prune._grow[int(gr.name[1]), 6])   # elems is the unit's element count
+        assert n == int(opt._prune._grow["elems"][int(gr.name[1])])   # elems is the unit's element count
         want = np.stack([(p * p).sum(1), (gv * gv).sum(1), (p * gv).sum(1)], axis=1)
         absum = np.stack([(p * p).sum(1), (gv * gv).sum(1), np.abs(p * gv).sum(1)], axis=1)
         tol = n * 2.0 ** -53 * absum
@@ -319,15 +319,14 @@ def test_the_fold_gives_zeros_to_a_unit_whose_row_items_disagree(dev):
     items = pr._items.copy()
     base = np.cumsum([0] + list(C.ROWS))         # a group's row 0 in the items
     unit0 = np.cumsum([0] + list(C.UNITS))       # a group's unit 0 in the units
-    lo = 0xffffffff
     r = base[0] + 1 * 4 + 2                      # l0: head 1, section 0, j = 2 -> names group 2
-    items[r, 0] = (items[r, 0] & ~lo) | 2
+    items["group"][r] = 2
     r = base[1] + (1 * 2 + 0) * 64 + 7           # l1: head 0, section 1, j = 7 -> names the row after it
-    items[r, 0] = (items[r, 0] & lo) | ((int(items[r, 0] >> 32) + 1) << 32)
+    items["row"][r] += 1
     r = base[3] + (2 * 2 + 1) * 4 + 3            # l3: head 1, section 2, j = 3 -> carries unit 0
-    items[r, 1] = items[r, 1] & lo
+    items["link"][r] = 0
     bad = {unit0[0] + 1, unit0[1] + 0, unit0[3] + 1}
-    table = torch.from_numpy(items).to(dev)
+    table = torch.from_numpy(items.view(np.int64)).to(dev)
     out = torch.full_like(good, -1.0)
     lib = _lib.load()
     st = lib.qvit_prune_scores_fold(_lib._ptr(pr._gtable.dev), len(pr.groups), _lib._ptr(table), pr.nprunable_rows,

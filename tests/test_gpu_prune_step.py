@@ -370,19 +370,18 @@ def test_finish_kernel_branches_from_given_sums(dev):
     from quantized_vit_amd import _lib
     ng = len(FINISH)
     scal = torch.tensor([[1.0 / 127, 1.0, 1.0]] * ng, dtype=torch.float32, device=dev)
-    table = np.zeros((ng, 8), dtype=np.int64)
+    table = np.zeros(ng, dtype=_lib.PRUNE_GROUP_DTYPE)
     partials = np.zeros((3 * ng, 6))
     for i, (s, _) in enumerate(FINISH):
         base = scal.data_ptr() + 12 * i
-        table[i, 0:3] = (base, base + 4, base + 8)
-        table[i, 4] = 10 | (1 << 32)
-        table[i, 5] = (3 * i) | (3 << 32)
-        table[i, 6] = 5
+        G = table[i]
+        G["d"], G["qm"], G["t"] = base, base + 4, base + 8
+        G["rows"], G["joint"], G["red_begin"], G["red_count"], G["elems"] = 10, 1, 3 * i, 3, 5
         partials[3 * i:3 * i + 3] = np.asarray(s) * np.array([[0.5], [0.25], [0.25]])
     gamma = torch.zeros(ng, dtype=torch.float32, device=dev)
     info = torch.zeros(ng, dtype=torch.int32, device=dev)
-    _lib.prune_joint_finish(torch.from_numpy(table).to(dev), ng, torch.from_numpy(partials).to(dev), 3 * ng, 1e-2, 4, 1,
-                            4, 16, gamma, info)
+    _lib.prune_joint_finish(torch.from_numpy(table.view(np.int64)).to(dev), ng, torch.from_numpy(partials).to(dev),
+                            3 * ng, 1e-2, 4, 1, 4, 16, gamma, info)
     gamma, info, d = gamma.cpu().numpy(), info.cpu().numpy(), scal[:, 0].cpu().numpy()
     for i, (s, want) in enumerate(FINISH):
         ga, da, ia = R.gamma_d_scalar(*s, count=15, lr=1e-2, period=4, t=1, q_m=1.0, t_quant=1.0, min_bit=4,

@@ -1,5 +1,5 @@
 """Head-geometry prune groups without a GPU: tests/prune_heads_ref.py's permutation, the host's unit-to-row expansion
-and table filling (quantized_vit_amd.qat_optim.prune_tables), vit_head_prune_groups' declaration, the constructor's new
+and table filling (quantized_vit_amd.qat_prune.prune_tables), vit_head_prune_groups' declaration, the constructor's new
 rejections, compress_pruned_heads as tensor surgery on CPU modules, the exports, and the condition on the schedule
 test's inputs: the reference run prunes a head and leaves one in each block."""
 import re
@@ -19,7 +19,7 @@ GEOMS = [(2, 4), (3, 4), (2, 64), (3, 64)]
 
 @pytest.mark.parametrize("H,hd", GEOMS)
 def test_permutation_round_trips_and_a_unit_is_the_heads_rows(H, hd):
-    from quantized_vit_amd.qat_optim import unit_rows_of, units_view
+    from quantized_vit_amd.qat_prune import unit_rows_of, units_view
     K = 5
     w = torch.arange(3 * H * hd * K, dtype=torch.float32).reshape(3 * H * hd, K)
     b = torch.arange(3 * H * hd, dtype=torch.float32)
@@ -43,17 +43,22 @@ def test_permutation_round_trips_and_a_unit_is_the_heads_rows(H, hd):
 
 
 def _states(groups):
-    from quantized_vit_amd.qat_optim import _GroupState
+    from quantized_vit_amd.qat_prune import _GroupState
     out = [_GroupState(g) for g in groups]
     for g in out:
         g.prunable = True
     return out
 
 
+def _i64(a):
+    """A descriptor array as the int64 words that reach the device, one row per descriptor."""
+    return a.view(np.int64).reshape(len(a), a.dtype.itemsize // 8)
+
+
 @pytest.mark.parametrize("H,hd", GEOMS)
 def test_table_filling(H, hd):
     from quantized_vit_amd import PruneGroup, _lib
-    from quantized_vit_amd.qat_optim import prune_tables
+    from quantized_vit_amd.qat_prune import prune_tables
     K = 3
     head = PruneGroup("h", None, [torch.zeros(3 * H * hd, K), torch.zeros(3 * H * hd)], sections=3, unit_rows=hd)
     basic = PruneGroup("b", None, [torch.zeros(6, K)])
@@ -62,8 +67,14 @@ def test_table_filling(H, hd):
     assert (gs[1].rows, gs[1].num_groups, gs[1].basic) == (3 * H * hd, H, False)
     gs[0].active, gs[0].pruned = [4, 1], [0]
     gs[1].active, gs[1].pruned = [H - 1], [0] if H > 2 else []
-    grow = np.zeros((2, 8), dtype=np.int64)
+    grow = np.zeros(2, dtype=_lib.PRUNE_GROUP_DTYPE)
     t = prune_tables(gs, [0, 1], True, grow)
+    assert all(t[k].dtype == _lib.PRUNE_ITEM_DTYPE for k in ("items", "units", "red"))
+    assert t["items"]["row"][:6].tolist() == list(range(6)) and t["red"]["row"][:2].tolist() == [4, 1]
+    assert grow["rows"].tolist() == [6, 3 * H * hd] and grow["joint"].tolist() == [1, 1]
+    assert grow["red_begin"].tolist() == [0, 2] and grow["red_count"].tolist() == [2, 3 * hd]
+    grow = _i64(grow)
+    t = {k: v if k == "joint" else _i64(v) for k, v in t.items()}   # the packed words, as the tables were before
 
     def split(a):
         return a[:, 0] & 0xffffffff, a[:, 0] >> 32, a[:, 1] & 0xffffffff, a[:, 1] >> 32
@@ -91,7 +102,8 @@ def test_table_filling(H, hd):
     # one-row groups alone: the tables of before (no link anywhere, no unit table)
     gs = _states([basic])
     gs[0].active = [2]
-    t = prune_tables(gs, [0], False, np.zeros((1, 8), dtype=np.int64))
+    t = prune_tables(gs, [0], False, np.zeros(1, dtype=_lib.PRUNE_GROUP_DTYPE))
+    t = {k: v if k == "joint" else _i64(v) for k, v in t.items()}
     assert (t["items"][:, 1] >> 32 == 0).all() and t["units"].shape == (0, 2) and t["red"].tolist() == [[2 << 32, 1]]
 
 
@@ -115,7 +127,7 @@ def test_vit_head_prune_groups_declares_the_forwards_heads():
 
 def test_constructor_rejections_of_the_new_geometry():
     from quantized_vit_amd import PruneGroup
-    from quantized_vit_amd.qat_optim import _check_prune_groups
+    from quantized_vit_amd.qat_prune import _check_prune_groups
     net = C.make_net(torch.device("cpu"))
     ok = PruneGroup("g", net.l0, [net.l0.weight, net.l0.bias], sections=3, unit_rows=4)
     _check_prune_groups([ok])
@@ -220,7 +232,7 @@ def test_the_declared_vit_groups_are_the_references_and_its_run_prunes_heads_und
     alone ranks heads among the MLP units; with it every head is selected and the group_divisible refinement gives one
     back per block."""
     from quantized_vit_amd import vit_head_prune_groups, vit_mlp_prune_groups
-    from quantized_vit_amd.qat_optim import _GroupState
+    from quantized_vit_amd.qat_prune import _GroupState
     from test_gpu_prune_step import NSTEPS, SCHEDULE
     model = C.head_vit(torch.device("cpu"))
     names = {id(p): n for n, p in model.named_parameters()}

@@ -26,7 +26,7 @@ from qat_step_bench import MODELS, build_model, device_ms, wall_ms   # noqa: E40
 
 from quantized_vit_amd import (QuantAwareOptimizer, _lib, build, compress_pruned_heads, vit_head_prune_groups,   # noqa: E402
                                vit_mlp_prune_groups, vit_model)
-from quantized_vit_amd.qat_optim import unit_rows_of   # noqa: E402
+from quantized_vit_amd.qat_prune import unit_rows_of   # noqa: E402
 
 
 def joint(model, groups, a):
@@ -38,8 +38,8 @@ def joint(model, groups, a):
     t = wall_ms(opt.step, a.warmup, a.reps)
     assert pr._nred and pr.curr_period == 1, "the timed steps were not joint steps"
     ng, hyper = len(pr.groups), opt._hyper(False)
-    member_n = sum(g.num_groups * int(pr._grow[i, 6]) for i, g in enumerate(pr.groups))
-    red_n = sum(len(g.active) * int(pr._grow[i, 6]) for i, g in enumerate(pr.groups))
+    member_n = sum(g.num_groups * int(pr._grow["elems"][i]) for i, g in enumerate(pr.groups))
+    red_n = sum(len(g.active) * int(pr._grow["elems"][i]) for i, g in enumerate(pr.groups))
     t_apply = device_ms(lambda: _lib.prune_joint_apply(pr._gtable.dev, ng, pr._mtable.dev, pr.nmembers, pr._itable.dev,
                                                        pr.nrows, pr.gamma, hyper), a.warmup, a.reps)
     t_reduce = device_ms(lambda: _lib.prune_joint_reduce(pr._gtable.dev, ng, pr._mtable.dev, pr.nmembers,

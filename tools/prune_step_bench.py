@@ -83,8 +83,8 @@ def main():
         t_joint = wall_ms(opt.step, a.warmup, a.reps)
         assert pr._nred and pr.curr_period == 1, "the timed steps were not joint steps"
         ng, hyper = len(pr.groups), opt._hyper(False)
-        member_n = sum(g.num_groups * int(pr._grow[i, 6]) for i, g in enumerate(pr.groups))
-        red_n = sum(len(g.active) * int(pr._grow[i, 6]) for i, g in enumerate(pr.groups))
+        member_n = sum(g.num_groups * int(pr._grow["elems"][i]) for i, g in enumerate(pr.groups))
+        red_n = sum(len(g.active) * int(pr._grow["elems"][i]) for i, g in enumerate(pr.groups))
         t_apply = device_ms(lambda: _lib.prune_joint_apply(pr._gtable.dev, ng, pr._mtable.dev, pr.nmembers,
                                                            pr._itable.dev, pr.nrows, pr.gamma, hyper),
                             a.warmup, a.reps)
