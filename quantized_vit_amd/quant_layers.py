@@ -390,6 +390,16 @@ class QuantPlan:
         """The plan holds packed weight codes (integer path or weight-only GEMM), so packed_t() can transpose them."""
         return self.int_path or bool(self.extra.get("wonly"))
 
+    @property
+    def act_q(self) -> tuple:
+        """The activation quantizer as the kernels' wrappers take it: (qtype, d, q_m, t)."""
+        return self.qtype, self.d_act, self.qm_act, self.t_act
+
+    @property
+    def wt_q(self) -> tuple:
+        """The weight quantizer, in the same order."""
+        return self.qtype, self.d_wt, self.qm_wt, self.t_wt
+
     def __deepcopy__(self, memo):
         # a copied layer has parameters at other addresses: it builds its own plan (and copies no device images)
         return None
@@ -721,7 +731,7 @@ class QuantizeMixin:
         if codes is not None:
             k = codes.to(device=plan.device, dtype=torch.float32)
             return (plan.d_wt * k).view_as(self.weight)      # d_w * k, as quantize_weight returns it
-        return _lib.fake_quant_f32(self.weight.detach().float(), plan.qtype, plan.d_wt, plan.qm_wt, plan.t_wt)
+        return _lib.fake_quant_f32(self.weight.detach().float(), *plan.wt_q)
 
     def weight_codes(self) -> torch.Tensor:
         """The integer weight codes the device path uses ([N, K] float32 on the device): the loaded ones
@@ -828,7 +838,7 @@ class QuantizeMixin:
         w_q = self.w_fakequant(plan).view_as(weight) if need_xq and not hip_x else None
         x_q = None
         if need_wq and not hip_w:
-            x_q = _lib.fake_quant_f32(xf, plan.qtype, plan.d_act, plan.qm_act, plan.t_act) if wa else xf
+            x_q = _lib.fake_quant_f32(xf, *plan.act_q) if wa else xf
         act_done = ()   # QuantizeConv2d's dgrad: the activation quantizer's backward ran with it, (its scalars,)
         if hip_x or hip_w:
             grad_xq, grad_wq, *act_done = self._gemm_grads_hip(plan, xf, x_q, w_q, G, hip_x, hip_w)
@@ -839,14 +849,14 @@ class QuantizeMixin:
         if need_aq and act_done:
             quantizers.append(("act", act_done[0]))
         elif need_aq:
-            grad_x, scal = _lib.quant_backward(xf, grad_xq, plan.qtype, plan.d_act, plan.qm_act, plan.t_act,
-                                               self.act_clip_val[0], self.act_clip_val[1], grad_x=grad_xq)
+            grad_x, scal = _lib.quant_backward(xf, grad_xq, *plan.act_q, self.act_clip_val[0], self.act_clip_val[1],
+                                               grad_x=grad_xq)
             quantizers.append(("act", scal))
         grad_w = None
         if need_wq:
             wf = weight.detach().float().contiguous()
-            grad_w, scal = _lib.quant_backward(wf, grad_wq, plan.qtype, plan.d_wt, plan.qm_wt, plan.t_wt,
-                                               self.weight_clip_val[0], self.weight_clip_val[1], grad_x=grad_wq)
+            grad_w, scal = _lib.quant_backward(wf, grad_wq, *plan.wt_q, self.weight_clip_val[0],
+                                               self.weight_clip_val[1], grad_x=grad_wq)
             quantizers.append(("wt", scal))
         scalars = self._checked_scalars(plan, quantizers)
         out = [grad_x.view_as(x).to(x.dtype) if need_x else None,
@@ -884,7 +894,7 @@ class QuantizeMixin:
     def _act_codes(self, x2d: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
         M = x2d.shape[0]
         codes = torch.empty((M, plan.kpad), dtype=torch.int8, device=x2d.device)
-        _lib.quantize_act_i8(x2d, plan.qtype, plan.d_act, plan.qm_act, plan.t_act, 0, codes, plan.kpad)
+        _lib.quantize_act_i8(x2d, *plan.act_q, 0, codes, plan.kpad)
         return codes
 
     def gemm_codes(self, codes: torch.Tensor, plan: QuantPlan, epilogue: int = _lib.EPI_F32,
@@ -895,13 +905,12 @@ class QuantizeMixin:
             _warn_no_grad()   # a direct low-level call: only the modules' forward() records autograd history
         M = codes.shape[0]
         dev = codes.device
-        oq = dict(out_qtype=0)
+        out_q, table = (0, None, None, None), None
         if epilogue in (_lib.EPI_I8, _lib.EPI_I8_GELU):
             nplan = next_layer.quant_plan()
             if out is None:
                 out = torch.empty((M, _round_up(plan.n, 16)), dtype=torch.int8, device=dev)
-            oq = dict(out_qtype=nplan.qtype, out_d=nplan.d_act, out_qm=nplan.qm_act, out_t=nplan.t_act,
-                      epi_table=epilogue_table(nplan, epilogue))
+            out_q, table = nplan.act_q, epilogue_table(nplan, epilogue)
         elif epilogue == _lib.EPI_I32:
             if out is None:
                 out = torch.empty((M, _round_up(plan.n, 4)), dtype=torch.int32, device=dev)
@@ -909,7 +918,7 @@ class QuantizeMixin:
             out = torch.empty((M, _round_up(plan.n, 4)), dtype=torch.float32, device=dev)
         wimg, wfmt = plan.gemm_weights()
         _lib.gemm(codes, M, plan.kpad, wimg, wfmt, plan.n, plan.npad, plan.d_act, plan.d_wt,
-                  plan.bias_pad, epilogue, out, **oq)
+                  plan.bias_pad, epilogue, out, *out_q, epi_table=table)
         return out
 
     def a32_fits(self, plan: QuantPlan, epilogue: int) -> bool:
@@ -922,8 +931,7 @@ class QuantizeMixin:
         schedule, same codes as gemm_codes on the row-major codes)."""
         nplan = next_layer.quant_plan()
         _lib.gemm_a32(codes_t32, M, plan.kpad, plan.packed_codes(), plan.wfmt, plan.n, plan.npad, plan.d_act, plan.d_wt,
-                      plan.bias_pad, epilogue, out, out_qtype=nplan.qtype, out_d=nplan.d_act, out_qm=nplan.qm_act,
-                      out_t=nplan.t_act, epi_table=epilogue_table(nplan, epilogue))
+                      plan.bias_pad, epilogue, out, *nplan.act_q, epi_table=epilogue_table(nplan, epilogue))
         return out
 
 
@@ -988,7 +996,7 @@ def epilogue_table(nplan: QuantPlan, epilogue: int) -> Optional[torch.Tensor]:
         host = nplan.extra.get("act_host")
         geo = epilogue_table_geometry(*host, gelu=epilogue == _lib.EPI_I8_GELU) if host else None
         nplan.extra[key] = None if geo is None else _lib.epi_table_build(
-            epilogue, nplan.qtype, nplan.d_act, nplan.qm_act, nplan.t_act, 0, geo[0], geo[1], geo[2], nplan.device)
+            epilogue, *nplan.act_q, 0, geo[0], geo[1], geo[2], nplan.device)
     return nplan.extra[key]
 
 
@@ -1102,7 +1110,7 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
         if need_pre:
             grad_xq = self._dgrad_hip(plan, G2)
             x2 = x.detach().reshape(-1, plan.k)
-            qargs = (plan.qtype, plan.d_act, plan.qm_act, plan.t_act, self.act_clip_val[0], self.act_clip_val[1])
+            qargs = (*plan.act_q, self.act_clip_val[0], self.act_clip_val[1])
             if eps is not None:
                 grad_x, grad_g, grad_bt, scal = _lib.layernorm_quant_backward(
                     x2, gamma.detach(), beta.detach(), eps, *qargs, grad_y=grad_xq, grad_x=grad_xq,
@@ -1114,8 +1122,8 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
         if need_wq:
             grad_wq = _lib.gemm_wgrad(G2, codes, plan.k, plan.d_act)
             wf = weight.detach().float().contiguous()
-            grad_w, scal = _lib.quant_backward(wf, grad_wq, plan.qtype, plan.d_wt, plan.qm_wt, plan.t_wt,
-                                               self.weight_clip_val[0], self.weight_clip_val[1], grad_x=grad_wq)
+            grad_w, scal = _lib.quant_backward(wf, grad_wq, *plan.wt_q, self.weight_clip_val[0],
+                                               self.weight_clip_val[1], grad_x=grad_wq)
             quantizers.append(("wt", scal))
         scalars = self._checked_scalars(plan, quantizers)
         return (grad_x.view_as(x).to(x.dtype) if need_x else None,
@@ -1175,10 +1183,9 @@ class _PreOpLinearFunction(torch.autograd.Function):
         M = x2.shape[0]
         codes = torch.empty((M, plan.kpad), dtype=torch.int8, device=x2.device)
         if eps is not None:
-            _lib.layernorm_quant_i8(x2, gamma.detach(), beta.detach(), eps, plan.qtype, plan.d_act, plan.qm_act,
-                                    plan.t_act, 0, codes, plan.kpad)
+            _lib.layernorm_quant_i8(x2, gamma.detach(), beta.detach(), eps, *plan.act_q, 0, codes, plan.kpad)
         else:
-            _lib.gelu_quant_i8(x2, plan.qtype, plan.d_act, plan.qm_act, plan.t_act, 0, codes, plan.kpad)
+            _lib.gelu_quant_i8(x2, *plan.act_q, 0, codes, plan.kpad)
         trace_codes(layer, codes, plan.k)
         out = layer.gemm_codes(codes, plan, _lib.EPI_F32)
         if out.shape[1] != plan.n:
@@ -1313,7 +1320,7 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
         T = None
         if plan.int_path:
             T = torch.empty((V.shape[0], 256), dtype=torch.int8, device=plan.device)
-            _lib.quantize_act_i8(V, plan.qtype, plan.d_act, plan.qm_act, plan.t_act, 0, T, 256)
+            _lib.quantize_act_i8(V, *plan.act_q, 0, T, 256)
         plan.extra["u8_tables"] = (key, V, T)
         return V, T
 
@@ -1334,8 +1341,7 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
         if u8:
             _lib.im2col_u8_i8(x, kh, kw, sh, sw, ph, pw, dh, dw, self._u8_tables(plan)[1], codes, plan.kpad)
         else:
-            _lib.im2col_quant_i8(x, kh, kw, sh, sw, ph, pw, dh, dw, plan.qtype, plan.d_act, plan.qm_act, plan.t_act,
-                                 0, codes, plan.kpad)
+            _lib.im2col_quant_i8(x, kh, kw, sh, sw, ph, pw, dh, dw, *plan.act_q, 0, codes, plan.kpad)
         trace_codes(self, codes, plan.k)
         out = self.gemm_codes(codes, plan, epilogue)
         return out, (B, OH, OW)
@@ -1402,8 +1408,7 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
             # P = G2 @ (d_wt k_w), then col2im; on a W+A layer the same pass applies quantize_act's backward
             P = self._dgrad_hip(plan, G2)
             if self.quant_mode == QuantizationMode.WEIGHT_AND_ACTIVATION:
-                grad_xq, scal = _lib.col2im_quant_backward(P, xf, xf.shape, *geometry, plan.qtype, plan.d_act,
-                                                           plan.qm_act, plan.t_act, *self.act_clip_val)
+                grad_xq, scal = _lib.col2im_quant_backward(P, xf, xf.shape, *geometry, *plan.act_q, *self.act_clip_val)
                 act_done = (scal,)
             else:
                 grad_xq, _ = _lib.col2im_quant_backward(P, None, xf.shape, *geometry)
@@ -1411,8 +1416,7 @@ class QuantizeConv2d(nn.Conv2d, QuantizeMixin):
             # G2^T @ (d_act codes): the forward's own im2col kernel recomputes the codes it contracted
             (kh, kw), (sh, sw), (ph, pw), (dh, dw) = geometry
             codes = torch.empty((G2.shape[0], plan.kpad), dtype=torch.int8, device=xf.device)
-            _lib.im2col_quant_i8(xf, kh, kw, sh, sw, ph, pw, dh, dw, plan.qtype, plan.d_act, plan.qm_act, plan.t_act,
-                                 0, codes, plan.kpad)
+            _lib.im2col_quant_i8(xf, kh, kw, sh, sw, ph, pw, dh, dw, *plan.act_q, 0, codes, plan.kpad)
             grad_wq = _lib.gemm_wgrad(G2, codes, plan.k, plan.d_act).view(self.weight.shape)
         return (grad_xq, grad_wq) + act_done
 

@@ -21,6 +21,7 @@ quantized layers differentiate through quant_layers' autograd node and the atten
 from __future__ import annotations
 
 from collections import OrderedDict
+from contextlib import nullcontext
 from functools import partial
 from typing import Optional
 
@@ -83,6 +84,27 @@ class _timed:
             e1 = torch.cuda.Event(enable_timing=True)
             e1.record()
             self.ev.append((self.e0, e1))
+
+
+def _code_buffer(rows: int, kpad: int, valid: int, device) -> torch.Tensor:
+    """int8 [rows, kpad] for a kernel that writes the codes of columns < valid: the padding columns are zeroed here."""
+    buf = torch.empty((rows, kpad), dtype=torch.int8, device=device)
+    if kpad != valid:
+        buf[:, valid:].zero_()
+    return buf
+
+
+def _ln_args(norm: nn.LayerNorm, p) -> tuple:
+    """`norm` followed by plan p's activation quantizer, as the LayerNorm kernels' wrappers take them."""
+    return (norm.weight, norm.bias, norm.eps, *p.act_q, 0)
+
+
+def _ln_codes(norm: nn.LayerNorm, x2: torch.Tensor, p, name: str) -> torch.Tensor:
+    """norm(x2) quantized for plan p -> fresh int8 codes [rows, p.kpad]; timed as `name` ("ln" or "ln_cls")."""
+    codes = torch.empty((x2.shape[0], p.kpad), dtype=torch.int8, device=x2.device)
+    with _timed(name):
+        _lib.layernorm_quant_i8(x2, *_ln_args(norm, p), codes, p.kpad, code_table=epilogue_table(p, _lib.EPI_I8))
+    return codes
 
 
 def drop_path(x, drop_prob: float = 0., training: bool = False):
@@ -149,6 +171,7 @@ def _pow2_grad_scale(gmax: float) -> float:
 
 
 HIP_HEAD_DIMS = (64, 80)   # head sizes of qvit_attention (fp32 output) and qvit_attention_backward
+ROUTE_FUSED, ROUTE_SPLIT, ROUTE_ATTENTION_I8, ROUTE_CORE = "fused", "split", "attention_i8", "core"   # fused_route
 
 
 def _attention_core_forward(q2: torch.Tensor, B: int, N: int, H: int, scale: float, hd: int):
@@ -213,14 +236,27 @@ class ViTAttention(nn.Module):
         return (self.head_dim in (64, 80) and p_qkv.n == 3 * self.num_heads * self.head_dim
                 and not (self.training and self.attn_drop.p > 0))
 
+    def fused_route(self, p_qkv, N: int) -> str:
+        """How the fused block gets from norm1's codes to proj's, for qkv plan `p_qkv` and N tokens:
+          ROUTE_FUSED         qvit_qkv_attention (last block: qvit_qkv_attention_q), all in one kernel
+          ROUTE_SPLIT         qvit_gemm_qkv_split (fp16 hi/lo head planes) -> qvit_attention_split
+          ROUTE_ATTENTION_I8  qvit_gemm (fp32 qkv) -> qvit_attention writing proj's codes
+          ROUTE_CORE          qvit_gemm (fp32 qkv) -> core() in fp32 -> proj's quantizer (qvit_quantize_act_i8)"""
+        if self.split_ok(p_qkv):
+            fused = (self.head_dim == 64 and N <= _lib.QKV_ATT_MAX_N and p_qkv.wfmt == _lib.W4
+                     and p_qkv.kpad <= 65536 and p_qkv.kpad % 256 == 0 and self.num_heads * 64 <= _lib.QKV_ATT_MAX_C)
+            return ROUTE_FUSED if fused else ROUTE_SPLIT
+        # hip_ok(qkv) and head_dim == 64, ahead of the GEMM: its fp32 output is a fresh [M, >= n] device buffer with
+        # unit column stride, so only hip_ok's conditions on the module are open (the chain asserts the rest)
+        hip = self.head_dim == 64 and not (self.training and self.attn_drop.p > 0)
+        return ROUTE_ATTENTION_I8 if hip else ROUTE_CORE
+
     def core_hip(self, qkv: torch.Tensor, B: int, N: int, out: torch.Tensor, out_mode: int = _lib.ATT_F32,
                  in_scale: float = 1.0, plan=None) -> torch.Tensor:
         """The same op on the fused HIP kernel (qvit_attention); with out_mode ATT_I8 it also applies the
         activation quantizer of `plan` (the proj layer) and writes its int8 codes (head_dim 64 only)."""
-        if out_mode == _lib.ATT_I8:
-            return _lib.attention(qkv, B, N, self.num_heads, self.head_dim, self.scale, out, out_mode, in_scale,
-                                  plan.qtype, plan.d_act, plan.qm_act, plan.t_act)
-        return _lib.attention(qkv, B, N, self.num_heads, self.head_dim, self.scale, out, out_mode, in_scale)
+        out_q = plan.act_q if out_mode == _lib.ATT_I8 else ()
+        return _lib.attention(qkv, B, N, self.num_heads, self.head_dim, self.scale, out, out_mode, in_scale, *out_q)
 
     def core(self, qkv: torch.Tensor, B: int, N: int) -> torch.Tensor:
         """softmax(q k^T * scale) v on the qkv projection (vit_model.py:133-149), fp32."""
@@ -341,10 +377,18 @@ class Block(nn.Module):
         M, C = x2.shape
         out = torch.empty((M, p_next.kpad), dtype=torch.int8, device=x2.device)
         _lib.gemm_resid_ln(codes_in, M, p_res.kpad, p_res.packed_codes(), p_res.wfmt, p_res.n, p_res.npad, p_res.d_act,
-                           p_res.d_wt, p_res.bias_pad, x2, norm.weight, norm.bias, norm.eps, p_next.qtype,
-                           p_next.d_act, p_next.qm_act, p_next.t_act, 0, epilogue_table(p_next, _lib.EPI_I8), out,
-                           p_next.kpad)
+                           p_res.d_wt, p_res.bias_pad, x2, *_ln_args(norm, p_next), epilogue_table(p_next, _lib.EPI_I8),
+                           out, p_next.kpad)
         return out
+
+    def _resid_gemm_(self, layer: QuantizeLinear, p: QuantPlan, codes: torch.Tensor, x2: torch.Tensor,
+                     norm: Optional[nn.LayerNorm] = None, next_layer: Optional[QuantizeLinear] = None):
+        """x2 += layer(codes) (proj / fc2, plan p). Given `norm` and ln_fusable (FUSE_RESID_LN), the same launch also runs
+        norm + next_layer's activation quantizer on the new rows and its codes are returned; else None."""
+        if norm is not None and self.ln_fusable(x2, norm, p):
+            return self.resid_ln_(codes, p, x2, norm, next_layer.quant_plan())
+        layer.gemm_codes(codes, p, _lib.EPI_F32_RESID, out=x2)
+        return None
 
     def _cls_tail_(self, x: torch.Tensor, cls_codes: torch.Tensor, nt: int):
         """The rest of the last block (proj, norm2, fc1, fc2) on the first `nt` token rows of every image only:
@@ -357,166 +401,121 @@ class Block(nn.Module):
         p_proj, p_fc1, p_fc2 = a.proj.quant_plan(), m.fc1.quant_plan(), m.fc2.quant_plan()
         xc = x[:, 0] if nt == 1 else x[:, :nt].reshape(B * nt, C)
         with _timed("proj_cls"):
-            a.proj.gemm_codes(cls_codes, p_proj, _lib.EPI_F32_RESID, out=xc)
-        codes = torch.empty((B * nt, p_fc1.kpad), dtype=torch.int8, device=x.device)
-        with _timed("ln_cls"):
-            _lib.layernorm_quant_i8(xc, self.norm2.weight, self.norm2.bias, self.norm2.eps, p_fc1.qtype,
-                                    p_fc1.d_act, p_fc1.qm_act, p_fc1.t_act, 0, codes, p_fc1.kpad,
-                                    code_table=epilogue_table(p_fc1, _lib.EPI_I8))
-        hid = torch.empty((B * nt, p_fc2.kpad), dtype=torch.int8, device=x.device)
-        if p_fc2.kpad != p_fc1.n:
-            hid[:, p_fc1.n:].zero_()
+            self._resid_gemm_(a.proj, p_proj, cls_codes, xc)
+        codes = _ln_codes(self.norm2, xc, p_fc1, "ln_cls")
+        hid = _code_buffer(B * nt, p_fc2.kpad, p_fc1.n, x.device)
         with _timed("fc1_cls"):
             m.fc1.gemm_codes(codes, p_fc1, _lib.EPI_I8_GELU, out=hid, next_layer=m.fc2)
         with _timed("fc2_cls"):
-            m.fc2.gemm_codes(hid, p_fc2, _lib.EPI_F32_RESID, out=xc)
+            self._resid_gemm_(m.fc2, p_fc2, hid, xc)
         return (x if nt == 1 else xc.view(B, nt, C)), None
-
-    @staticmethod
-    def _cls_rows(codes: torch.Tensor, B: int, N: int, nt: int) -> torch.Tensor:
-        """The first nt rows of every image of full-M codes [B*N, ld]: a strided view (lda = N*ld) for nt = 1."""
-        c3 = codes.view(B, N, codes.shape[1])
-        return c3[:, 0] if nt == 1 else c3[:, :nt].reshape(B * nt, codes.shape[1])
 
     def forward_fused_chain_(self, x: torch.Tensor, codes_in: Optional[torch.Tensor] = None,
                              next_block: Optional["Block"] = None, last: bool = False, num_tokens: int = 1):
-        """forward_fused_ with the LayerNorms carried by the residual GEMMs: `codes_in` = this block's norm1
-        codes when the previous block's fc2 produced them; with `next_block`, fc2 also produces that block's
-        norm1 codes. Returns (x, next_block's norm1 codes or None).
+        """The fused block in place on the residual buffer x: norm1's codes (`codes_in` when the previous block's fc2
+        produced them, FUSE_RESID_LN), the attention launches of ViTAttention.fused_route (_attention_codes_), then one
+        tail: proj into x and _mlp_fused_, whose fc2 can produce `next_block`'s norm1 codes. Returns (x, those or None).
         `last`: this is the model's last block and only the first `num_tokens` token rows of its output are read
         (LAST_BLOCK_CLS_ONLY): everything after the keys and values is computed for those rows only (_cls_tail_),
         and only they are valid in the returned x ([B, N, C] for num_tokens = 1, else [B, num_tokens, C])."""
         B, N, C = x.shape
-        M = B * N
-        x2 = x.view(M, C)
-        a, m = self.attn, self.mlp
-        # x + attn(norm1(x))
+        x2 = x.view(B * N, C)
+        a = self.attn
         p_qkv = a.qkv.quant_plan()
-        if codes_in is not None:
-            codes = codes_in
-        else:
-            codes = torch.empty((M, p_qkv.kpad), dtype=torch.int8, device=x.device)
-            with _timed("ln"):
-                _lib.layernorm_quant_i8(x2, self.norm1.weight, self.norm1.bias, self.norm1.eps, p_qkv.qtype,
-                                        p_qkv.d_act, p_qkv.qm_act, p_qkv.t_act, 0, codes, p_qkv.kpad,
-                                        code_table=epilogue_table(p_qkv, _lib.EPI_I8))
-        trace_codes(a.qkv, codes, C)
+        # x + attn(norm1(x))
+        ln_codes = codes_in if codes_in is not None else _ln_codes(self.norm1, x2, p_qkv, "ln")
+        trace_codes(a.qkv, ln_codes, C)   # (ln_codes is held to the end of the block: DESIGN.md section 4, lifetimes)
         p_proj = a.proj.quant_plan()
-        if (a.split_ok(p_qkv) and a.head_dim == 64 and N <= _lib.QKV_ATT_MAX_N and p_qkv.wfmt == _lib.W4
-                and p_qkv.kpad <= 65536
-                and p_qkv.kpad % 256 == 0 and a.num_heads * 64 <= _lib.QKV_ATT_MAX_C):
-            # qkv projection + attention + proj's activation quantizer in one kernel (q/k/v stay on chip)
-            # (last: compact [B*nt, kpad], the wanted queries only)
-            out = torch.empty((B * num_tokens if last else M, p_proj.kpad), dtype=torch.int8, device=x.device)
-            if p_proj.kpad != a.num_heads * 64:
-                out[:, a.num_heads * 64:].zero_()
+        route = a.fused_route(p_qkv, N)
+        codes = self._attention_codes_(route, ln_codes, p_qkv, p_proj, B, N, last, num_tokens)
+        if last:
+            return self._cls_tail_(x, codes, num_tokens)
+        # Known oddities (DESIGN.md section 4): only the fused route's proj carries the "proj" timing events and may
+        # run norm2 behind its tiles; on the other routes it is the plain GEMM whatever FUSE_RESID_LN says.
+        fused = route == ROUTE_FUSED
+        with _timed("proj") if fused else nullcontext():
+            norm2_codes = self._resid_gemm_(a.proj, p_proj, codes, x2, norm=self.norm2 if fused else None,
+                                            next_layer=self.mlp.fc1)
+        return self._mlp_fused_(x, x2, norm2_codes, next_block)
+
+    def _attention_codes_(self, route: str, codes: torch.Tensor, p_qkv: QuantPlan, p_proj: QuantPlan, B: int, N: int,
+                          last: bool, num_tokens: int) -> torch.Tensor:
+        """The qkv projection and the attention core on norm1's `codes` by `route`. Returns proj's activation codes, of
+        every row or with `last` of the first `num_tokens` tokens of each image: compact from qvit_qkv_attention_q on
+        the fused route; on the others the attention runs in full and the rows are a view of its codes."""
+        a = self.attn
+        M, dev = B * N, codes.device
+        width = a.num_heads * a.head_dim   # proj's input columns; the rest of its kpad stays zero
+        if route == ROUTE_FUSED:   # q/k/v stay on chip
+            out = _code_buffer(B * num_tokens if last else M, p_proj.kpad, width, dev)
             in_scale, tab = attention_in_scale(p_qkv), epilogue_table(p_proj, _lib.EPI_I8)
-            if last:
+            args = (p_qkv.kpad, p_qkv.packed_codes(), p_qkv.npad, p_qkv.d_act, p_qkv.d_wt, p_qkv.bias_pad,
+                    a.num_heads, a.scale, out, _lib.ATT_I8, in_scale, *p_proj.act_q)
+            if last:   # the wanted queries only; not traced (last is off while codes are traced)
                 with _timed("qkv_attn_cls"):
-                    _lib.qkv_attention_q(codes, B, N, num_tokens, p_qkv.kpad, p_qkv.packed_codes(), p_qkv.npad,
-                                         p_qkv.d_act, p_qkv.d_wt, p_qkv.bias_pad, a.num_heads, a.scale, out,
-                                         _lib.ATT_I8, in_scale, p_proj.qtype, p_proj.d_act, p_proj.qm_act,
-                                         p_proj.t_act, epi_table=tab)
-                return self._cls_tail_(x, out, num_tokens)
+                    _lib.qkv_attention_q(codes, B, N, num_tokens, *args, epi_table=tab)
+                return out
             with _timed("qkv_attn"):
-                _lib.qkv_attention(codes, B, N, p_qkv.kpad, p_qkv.packed_codes(), p_qkv.npad, p_qkv.d_act, p_qkv.d_wt,
-                                   p_qkv.bias_pad, a.num_heads, a.scale, out, _lib.ATT_I8, in_scale,
-                                   p_proj.qtype, p_proj.d_act, p_proj.qm_act, p_proj.t_act, epi_table=tab)
-            trace_codes(a.proj, out, p_proj.k)
-            p_fc1 = m.fc1.quant_plan()
-            if self.ln_fusable(x2, self.norm2, p_proj):
-                with _timed("proj"):
-                    ln_codes = self.resid_ln_(out, p_proj, x2, self.norm2, p_fc1)
-                return self._mlp_fused_(x, x2, M, ln_codes, next_block)
-            with _timed("proj"):
-                a.proj.gemm_codes(out, p_proj, _lib.EPI_F32_RESID, out=x2)
-            return self._mlp_fused_(x, x2, M, None, next_block)
-        if a.split_ok(p_qkv):
-            # qkv as pre-scaled fp16 hi/lo head planes, then attention + proj's activation quantizer
+                _lib.qkv_attention(codes, B, N, *args, epi_table=tab)
+        elif route == ROUTE_SPLIT:   # qkv as pre-scaled fp16 hi/lo head planes
             in_scale = attention_in_scale(p_qkv)
-            hi = torch.empty(M * p_qkv.n, dtype=torch.float16, device=x.device)
-            lo = torch.empty(M * p_qkv.n, dtype=torch.float16, device=x.device)
+            hi = torch.empty(M * p_qkv.n, dtype=torch.float16, device=dev)
+            lo = torch.empty(M * p_qkv.n, dtype=torch.float16, device=dev)
             wimg, wfmt = p_qkv.gemm_weights()
             _lib.gemm_qkv_split(codes, M, p_qkv.kpad, wimg, wfmt, p_qkv.n, p_qkv.npad, p_qkv.d_act,
                                 p_qkv.d_wt, p_qkv.bias_pad, N, in_scale, hi, lo, head_dim=a.head_dim)
-            codes = torch.empty((M, p_proj.kpad), dtype=torch.int8, device=x.device)
-            if p_proj.kpad != a.num_heads * a.head_dim:
-                codes[:, a.num_heads * a.head_dim:].zero_()
-            _lib.attention_split(hi, lo, B, N, a.num_heads, a.head_dim, a.scale, codes, _lib.ATT_I8, in_scale,
-                                 p_proj.qtype, p_proj.d_act, p_proj.qm_act, p_proj.t_act,
-                                 epi_table=epilogue_table(p_proj, _lib.EPI_I8))
-            trace_codes(a.proj, codes, p_proj.k)
-            if last:   # the attention in full, the rest on the class rows (lda = N * kpad)
-                return self._cls_tail_(x, self._cls_rows(codes, B, N, num_tokens), num_tokens)
-            a.proj.gemm_codes(codes, p_proj, _lib.EPI_F32_RESID, out=x2)
-            return self._mlp_fused_(x, x2, M, None, next_block)
-        qkv = a.qkv.gemm_codes(codes, p_qkv, _lib.EPI_F32)
-        if qkv.shape[1] != p_qkv.n:
-            qkv = qkv[:, :p_qkv.n]
-        if a.hip_ok(qkv) and a.head_dim == 64:
-            # attention core + proj's activation quantizer in one kernel: int8 codes for the proj GEMM
-            # (head_dim 80 reaches this point only when split_ok is false: the fp32 core below, then proj's quantizer)
-            codes = torch.empty((M, p_proj.kpad), dtype=torch.int8, device=x.device)
-            if p_proj.kpad != a.num_heads * 64:
-                codes[:, a.num_heads * 64:].zero_()
-            a.core_hip(qkv, B, N, codes, _lib.ATT_I8, attention_in_scale(p_qkv), p_proj)
+            out = _code_buffer(M, p_proj.kpad, width, dev)
+            _lib.attention_split(hi, lo, B, N, a.num_heads, a.head_dim, a.scale, out, _lib.ATT_I8, in_scale,
+                                 *p_proj.act_q, epi_table=epilogue_table(p_proj, _lib.EPI_I8))
         else:
-            h = a.core(qkv, B, N).reshape(M, -1)
-            codes = a.proj._act_codes(h if h.is_contiguous() else h.contiguous(), p_proj)
-        trace_codes(a.proj, codes, p_proj.k)
-        if last:
-            return self._cls_tail_(x, self._cls_rows(codes, B, N, num_tokens), num_tokens)
-        a.proj.gemm_codes(codes, p_proj, _lib.EPI_F32_RESID, out=x2)
-        return self._mlp_fused_(x, x2, M, None, next_block)
+            qkv = a.qkv.gemm_codes(codes, p_qkv, _lib.EPI_F32)[:, :p_qkv.n]
+            if route == ROUTE_ATTENTION_I8:
+                assert a.hip_ok(qkv), "fused_route chose qvit_attention for a qkv layout it cannot read"
+                out = _code_buffer(M, p_proj.kpad, width, dev)
+                a.core_hip(qkv, B, N, out, _lib.ATT_I8, attention_in_scale(p_qkv), p_proj)
+            else:
+                h = a.core(qkv, B, N).reshape(M, -1)
+                out = a.proj._act_codes(h if h.is_contiguous() else h.contiguous(), p_proj)
+        trace_codes(a.proj, out, p_proj.k)
+        if last:   # the first num_tokens rows of every image of the full-M codes: a strided view (lda = N * kpad) for one
+            c3 = out.view(B, N, out.shape[1])
+            out = c3[:, 0] if num_tokens == 1 else c3[:, :num_tokens].reshape(B * num_tokens, out.shape[1])
+        return out
 
-    def _mlp_fused_(self, x: torch.Tensor, x2: torch.Tensor, M: int, codes_in: Optional[torch.Tensor] = None,
+    def _mlp_fused_(self, x: torch.Tensor, x2: torch.Tensor, codes_in: Optional[torch.Tensor] = None,
                     next_block: Optional["Block"] = None):
         """x + mlp(norm2(x)) in place on the residual buffer (codes_in: norm2's codes, from the proj GEMM).
         Returns (x, next_block's norm1 codes when fc2 produced them, else None)."""
         m = self.mlp
-        p_fc1 = m.fc1.quant_plan()
-        p_fc2 = m.fc2.quant_plan()
-        hid = torch.empty((M, p_fc2.kpad), dtype=torch.int8, device=x.device)
-        if p_fc2.kpad != p_fc1.n:
-            hid[:, p_fc1.n:].zero_()
+        p_fc1, p_fc2 = m.fc1.quant_plan(), m.fc2.quant_plan()
+        hid = _code_buffer(x2.shape[0], p_fc2.kpad, p_fc1.n, x.device)
         if (FC1_WEIGHT_STATIONARY and codes_in is None and m.fc1.a32_fits(p_fc1, _lib.EPI_I8_GELU)
                 and self.norm2.weight.is_contiguous()):
-            # norm2's codes in the MFMA operand order of the weight-stationary fc1 (qvit_gemm_a32): every fragment
-            # load of the GEMM one contiguous KiB
-            codes = torch.empty(_lib.t32_rows(M) * p_fc1.kpad, dtype=torch.int8, device=x.device)
-            with _timed("ln"):
-                _lib.layernorm_quant_i8_t32(x2, self.norm2.weight, self.norm2.bias, self.norm2.eps, p_fc1.qtype,
-                                            p_fc1.d_act, p_fc1.qm_act, p_fc1.t_act, 0, codes, p_fc1.kpad,
-                                            code_table=epilogue_table(p_fc1, _lib.EPI_I8))
-            if _ql.CODE_TRACE is not None:
-                trace_codes(m.fc1, _lib.t32_to_rows(codes, M, p_fc1.kpad), p_fc1.k)
-            with _timed("fc1"):
-                m.fc1.gemm_codes_a32(codes, M, p_fc1, _lib.EPI_I8_GELU, hid, m.fc2)
-            return self._fc2_fused_(x, x2, hid, p_fc2, next_block)
-        if codes_in is not None:
-            codes = codes_in
+            self._fc1_weight_stationary_(x2, p_fc1, hid)
         else:
-            codes = torch.empty((M, p_fc1.kpad), dtype=torch.int8, device=x.device)
-            with _timed("ln"):
-                _lib.layernorm_quant_i8(x2, self.norm2.weight, self.norm2.bias, self.norm2.eps, p_fc1.qtype,
-                                        p_fc1.d_act, p_fc1.qm_act, p_fc1.t_act, 0, codes, p_fc1.kpad,
-                                        code_table=epilogue_table(p_fc1, _lib.EPI_I8))
-        trace_codes(m.fc1, codes, p_fc1.k)
-        with _timed("fc1"):
-            m.fc1.gemm_codes(codes, p_fc1, _lib.EPI_I8_GELU, out=hid, next_layer=m.fc2)
-        return self._fc2_fused_(x, x2, hid, p_fc2, next_block)
-
-    def _fc2_fused_(self, x: torch.Tensor, x2: torch.Tensor, hid: torch.Tensor, p_fc2: QuantPlan,
-                    next_block: Optional["Block"] = None):
-        m = self.mlp
+            codes = codes_in if codes_in is not None else _ln_codes(self.norm2, x2, p_fc1, "ln")
+            trace_codes(m.fc1, codes, p_fc1.k)
+            with _timed("fc1"):
+                m.fc1.gemm_codes(codes, p_fc1, _lib.EPI_I8_GELU, out=hid, next_layer=m.fc2)
         trace_codes(m.fc2, hid, p_fc2.k)
-        if next_block is not None and self.ln_fusable(x2, next_block.norm1, p_fc2):
-            with _timed("fc2"):
-                nxt = self.resid_ln_(hid, p_fc2, x2, next_block.norm1, next_block.attn.qkv.quant_plan())
-            return x, nxt
         with _timed("fc2"):
-            m.fc2.gemm_codes(hid, p_fc2, _lib.EPI_F32_RESID, out=x2)
-        return x, None
+            if next_block is None:
+                return x, self._resid_gemm_(m.fc2, p_fc2, hid, x2)
+            return x, self._resid_gemm_(m.fc2, p_fc2, hid, x2, norm=next_block.norm1, next_layer=next_block.attn.qkv)
+
+    def _fc1_weight_stationary_(self, x2: torch.Tensor, p_fc1: QuantPlan, hid: torch.Tensor) -> None:
+        """FC1_WEIGHT_STATIONARY: norm2 writes its codes in the MFMA operand order of qvit_gemm_a32 (every fragment load
+        of that GEMM one contiguous KiB), which runs fc1 into `hid`."""
+        m = self.mlp
+        M = x2.shape[0]
+        codes = torch.empty(_lib.t32_rows(M) * p_fc1.kpad, dtype=torch.int8, device=x2.device)
+        with _timed("ln"):
+            _lib.layernorm_quant_i8_t32(x2, *_ln_args(self.norm2, p_fc1), codes, p_fc1.kpad,
+                                        code_table=epilogue_table(p_fc1, _lib.EPI_I8))
+        if _ql.CODE_TRACE is not None:
+            trace_codes(m.fc1, _lib.t32_to_rows(codes, M, p_fc1.kpad), p_fc1.k)
+        with _timed("fc1"):
+            m.fc1.gemm_codes_a32(codes, M, p_fc1, _lib.EPI_I8_GELU, hid, m.fc2)
 
     def forward_train_fused(self, x: torch.Tensor) -> torch.Tensor:
         """The modules route with the three LayerNorm / GELU -> QuantizeLinear sites as fused autograd nodes
