@@ -100,7 +100,28 @@ U8_MAX_C = 16   # channels whose [C][256] tables the uint8 kernels hold in LDS
 TILE_N = 256
 TILE_K = 128
 
-_c_p = ctypes.c_void_p
+
+def round_up(v: int, m: int) -> int:
+    return (v + m - 1) // m * m
+
+
+# Which of a layer's two backward contractions run on the project's kernels, by the value of its switch
+# (quant_layers.BACKWARD_GEMM / CONV_BACKWARD_GEMM, quant_ultra.ULTRA_BWD; the rules on top stay with the switches).
+BACKWARD_OPS = {"hip": ("dgrad", "wgrad"), "torch": (), "dgrad": ("dgrad",), "wgrad": ("wgrad",)}
+
+
+def backward_ops(value, what: str) -> tuple:
+    """BACKWARD_OPS[value]. `what` names where the value came from, for the error: an environment variable
+    (QVIT_..., checked at import, reported as NAME='v') or a module attribute (looked up at every use, since a caller
+    may have assigned it; reported as NAME = 'v')."""
+    try:
+        return BACKWARD_OPS[value]
+    except KeyError:
+        sep = "=" if what.startswith("QVIT_") else " = "
+        raise ValueError(f"{what}{sep}{value!r}: expected hip, torch, dgrad or wgrad") from None
+
+
+_c_p =ctypes.c_void_p
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int
 _f32 = ctypes.c_float
@@ -566,6 +587,21 @@ def pack_weight(w2d: torch.Tensor, qtype: int, d: torch.Tensor, qm: torch.Tensor
     return packed
 
 
+def code_quantizer(device: torch.device) -> tuple:
+    """(qtype, d, q_m, t) under which qvit_pack_weight reproduces integer-valued inputs exactly: the linear
+    quantizer at d = 1 rounds an integer to itself, and q_m = 1024 exceeds every int8 code, so nothing is clipped."""
+    return QT_LINEAR, torch.ones(1, device=device), torch.full((1,), 1024.0, device=device), None
+
+
+def pack_codes(codes: torch.Tensor, wfmt: int, npad: int, kpad: int,
+               overflow: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The W4 / W8 image of integer weight codes (fp32 [n, k] rows on the device), exact. `overflow`: the int32
+    word a code outside the format is counted in; without one a fresh word is used and nothing is read back."""
+    if overflow is None:
+        overflow = torch.zeros(1, dtype=torch.int32, device=codes.device)
+    return pack_weight(codes, *code_quantizer(codes.device), wfmt, npad, kpad, overflow)
+
+
 def pack_weight_w4r(packed: torch.Tensor, npad: int, kpad: int) -> torch.Tensor:
     """The register-weight image (wfmt W4R) of a W4 image from pack_weight (qvit_pack_weight_w4r): same bytes,
     re-ordered per GEMM lane; qvit_gemm gives the W4 results on it."""
@@ -606,10 +642,9 @@ def pack_weight_wide(codes: torch.Tensor, npad: int, kpad: int):
         r = (r - d) / 256.0                              # exact: r - d is a multiple of 256
     if float(r.abs().max()) if r.numel() else 0.0:
         raise QvitError("pack_weight_wide: codes do not fit the digits")
-    one = torch.ones(1, device=c.device)
-    big = torch.full((1,), 1024.0, device=c.device)
+    exact = code_quantizer(c.device)   # one pair of scalars and one overflow word for all the digits
     ovf = torch.zeros(1, dtype=torch.int32, device=c.device)
-    imgs = [pack_weight(d.contiguous(), QT_LINEAR, one, big, None, W8, npad, kpad, ovf) for d in reversed(digits)]
+    imgs = [pack_weight(d.contiguous(), *exact, W8, npad, kpad, ovf) for d in reversed(digits)]
     if int(ovf.item()) != 0:
         raise QvitError("pack_weight_wide: a digit left the int8 range")
     return torch.cat(imgs), (W16 if ndig == 2 else W24)
@@ -770,6 +805,31 @@ def gemm_wonly(X: torch.Tensor, M: int, K: int, packed: torch.Tensor, wfmt: int,
                                   _ptr(bias_pad), _ptr(Y), Y.stride(0), _ptr(ws), 0 if ws is None else ws.numel() * 4,
                                   _stream(X.device)), "qvit_gemm_wonly")
     return Y
+
+
+def gemm_wonly_rows(x2: torch.Tensor, k: int, kpad: int, packed: torch.Tensor, wfmt: int, n: int, npad: int,
+                    d_wt: torch.Tensor, bias_pad: Optional[torch.Tensor]) -> torch.Tensor:
+    """d_wt * (x2[:, :k] @ codes^T) + bias as [M, n] on qvit_gemm_wonly, for the rows of a layer's forward or the
+    output gradient of its backward against the (transposed) packed image. The rows are read in place when the kernel
+    can take them: fp32, unit column stride, at least kpad columns (those past k multiply zero codes), a row stride
+    that is a multiple of 4 and a 16-byte aligned base; otherwise their first k columns are copied into fresh
+    zero-padded [M, kpad] rows. The result is a view of rows of round_up(n, 4) floats when n is no multiple of 4.
+    It launches whenever it is called, on no rows too: a caller that must not checks M itself.
+
+    This one predicate is what each caller used to spell for the operands it can see: a gradient's width n never
+    exceeds kpad_t = round_up(n, TILE_K), and a layer's in_features never exceed its kpad, so `shape[1] >= kpad`
+    is `shape[1] == kpad` there; and a contiguous [M, kpad_t] matrix has a row stride that is a multiple of 4, so the
+    site that left the stride test out lost nothing."""
+    M = x2.shape[0]
+    if (x2.dtype != torch.float32 or x2.stride(-1) != 1 or x2.shape[1] < kpad or x2.stride(0) % 4
+            or x2.data_ptr() % 16):
+        rows = torch.zeros((M, kpad), dtype=torch.float32, device=x2.device)
+        rows[:, :k] = x2[:, :k]
+        x2 = rows
+    ldy = round_up(n, 4)
+    y = torch.empty((M, ldy), dtype=torch.float32, device=x2.device)
+    gemm_wonly(x2, M, kpad, packed, wfmt, n, npad, d_wt, bias_pad, y)
+    return y if ldy == n else y[:, :n]
 
 
 def gemm_wgrad_splits(M: int, N: int, K: int) -> int:

@@ -233,10 +233,6 @@ def _get_quantizer(qtype: QuantizationType):
     raise NotImplementedError
 
 
-def _round_up(v: int, m: int) -> int:
-    return (v + m - 1) // m * m
-
-
 # The int path's W4 GEMMs (qvit_gemm, qvit_gemm_qkv_split) take a register image of the packed codes (same
 # results, each GEMM wave's weight rows loaded into registers instead of through LDS): "w4r" (qvit_pack_weight_w4r,
 # the int4 bytes re-ordered; round 5: fc1 -2.6 % in the model) or "w8r" (qvit_pack_weight_w8r, the codes already
@@ -253,16 +249,11 @@ GEMM_W4R = GEMM_WREG != "w4"   # a register image is in use
 # integer path; "torch" keeps both on torch.mm (fp32 library GEMMs); "dgrad" / "wgrad" select one op.
 # QVIT_BWD_GEMM sets it (the measurement behind the default: DESIGN.md section 13).
 BACKWARD_GEMM = os.environ.get("QVIT_BWD_GEMM", "hip")
-_BACKWARD_GEMM_OPS = {"hip": ("dgrad", "wgrad"), "torch": (), "dgrad": ("dgrad",), "wgrad": ("wgrad",)}
-if BACKWARD_GEMM not in _BACKWARD_GEMM_OPS:
-    raise ValueError(f"QVIT_BWD_GEMM={BACKWARD_GEMM!r}: expected hip, torch, dgrad or wgrad")
+_lib.backward_ops(BACKWARD_GEMM, "QVIT_BWD_GEMM")   # an unknown value stops the import
 
 
 def _backward_gemm_ops() -> tuple:
-    try:
-        return _BACKWARD_GEMM_OPS[BACKWARD_GEMM]
-    except KeyError:
-        raise ValueError(f"BACKWARD_GEMM = {BACKWARD_GEMM!r}: expected hip, torch, dgrad or wgrad") from None
+    return _lib.backward_ops(BACKWARD_GEMM, "BACKWARD_GEMM")
 
 
 # The backward GEMMs of QuantizeConv2d (behind F.conv2d's backward), a switch of its own: "hip" runs both on the
@@ -275,17 +266,14 @@ def _backward_gemm_ops() -> tuple:
 # both on the library where taps overlap (P is then kh kw / (sh sw) times the image; the one 3 x 3 stride-1 layer
 # measured ran at a third of the library's speed on either op). QVIT_CONV_BWD_GEMM sets it.
 CONV_BACKWARD_GEMM = os.environ.get("QVIT_CONV_BWD_GEMM")
-if CONV_BACKWARD_GEMM is not None and CONV_BACKWARD_GEMM not in _BACKWARD_GEMM_OPS:
-    raise ValueError(f"QVIT_CONV_BWD_GEMM={CONV_BACKWARD_GEMM!r}: expected hip, torch, dgrad or wgrad")
+if CONV_BACKWARD_GEMM is not None:
+    _lib.backward_ops(CONV_BACKWARD_GEMM, "QVIT_CONV_BWD_GEMM")
 
 
 def _conv_backward_gemm_ops(overlap: bool) -> tuple:
     if CONV_BACKWARD_GEMM is None:
         return () if overlap else ("dgrad", "wgrad")
-    try:
-        return _BACKWARD_GEMM_OPS[CONV_BACKWARD_GEMM]
-    except KeyError:
-        raise ValueError(f"CONV_BACKWARD_GEMM = {CONV_BACKWARD_GEMM!r}: expected hip, torch, dgrad or wgrad") from None
+    return _lib.backward_ops(CONV_BACKWARD_GEMM, "CONV_BACKWARD_GEMM")
 
 
 def _wreg_unit_order(device: torch.device) -> torch.Tensor:
@@ -443,10 +431,10 @@ class QuantPlan:
     def packed_t(self) -> Tuple[torch.Tensor, int, int]:
         """(image, npad, kpad) of the TRANSPOSED weight codes in the plan's wfmt (rows = in-features padded to
         TILE_N, reduction = out-features padded to TILE_K): the operand of the input gradient on qvit_gemm_wonly.
-        Packed from codes() on the first backward and kept with the plan (whose key follows every parameter
-        update); packing integers with the linear quantizer at d = 1 reproduces them exactly."""
+        Packed from codes() on the first backward (_lib.pack_codes: exact) and kept with the plan (whose key follows
+        every parameter update)."""
         if "packed_t" not in self.extra:
-            npad_t, kpad_t = _round_up(self.k, _lib.TILE_N), _round_up(self.n, _lib.TILE_K)
+            npad_t, kpad_t = _lib.round_up(self.k, _lib.TILE_N), _lib.round_up(self.n, _lib.TILE_K)
             if "t_src" in self.extra:   # a training-mode plan: the weight of this very step (_build_plan)
                 src, qargs = self.extra["t_src"]
                 overflow = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -458,10 +446,7 @@ class QuantPlan:
                 image, wfmt = _lib.pack_weight_wide(ct, npad_t, kpad_t)
                 assert wfmt == self.wfmt
             else:
-                overflow = torch.zeros(1, dtype=torch.int32, device=self.device)
-                image = _lib.pack_weight(ct, _lib.QT_LINEAR, torch.ones(1, device=self.device),
-                                         torch.full((1,), 1024.0, device=self.device), None, self.wfmt, npad_t,
-                                         kpad_t, overflow)
+                image = _lib.pack_codes(ct, self.wfmt, npad_t, kpad_t)
             self.extra["packed_t"] = (image, npad_t, kpad_t)
         return self.extra["packed_t"]
 
@@ -514,49 +499,44 @@ class QuantizeMixin:
             return False
         return True
 
+    def _fake_quant(self, x: torch.Tensor, which: str, clip_val) -> torch.Tensor:
+        """The `which` ("wt" / "act") quantizer's values of x: the autograd function when history is wanted, else
+        the bare kernel."""
+        if self._records_grad(x):
+            return self._quantize_fn(x, which, clip_val)
+        d, qm, t = (_as_param_ptr(getattr(self, f"{name}_{which}", None), x.device)
+                    for name in ("d_quant", "q_m", "t_quant"))
+        return _lib.fake_quant_f32(x.detach(), _qtype_code(self.quant_type), d, qm, t)
+
     def quantize_weight(self, weight: torch.Tensor) -> torch.Tensor:
-        if self._records_grad(weight):
-            return self._quantize_fn(weight, "wt", self.weight_clip_val)
-        dev = weight.device
-        return _lib.fake_quant_f32(weight.detach(), _qtype_code(self.quant_type),
-                                   _as_param_ptr(self.d_quant_wt, dev), _as_param_ptr(self.q_m_wt, dev),
-                                   _as_param_ptr(getattr(self, "t_quant_wt", None), dev))
+        return self._fake_quant(weight, "wt", self.weight_clip_val)
 
     def quantize_act(self, activation: torch.Tensor) -> torch.Tensor:
         if self.quant_mode != QuantizationMode.WEIGHT_AND_ACTIVATION:
             return activation
-        if self._records_grad(activation):
-            return self._quantize_fn(activation, "act", self.act_clip_val)
-        dev = activation.device
-        return _lib.fake_quant_f32(activation.detach(), _qtype_code(self.quant_type),
-                                   _as_param_ptr(self.d_quant_act, dev), _as_param_ptr(self.q_m_act, dev),
-                                   _as_param_ptr(getattr(self, "t_quant_act", None), dev))
+        return self._fake_quant(activation, "act", self.act_clip_val)
 
-    @property
-    def weight_bit(self) -> int:
-        d = self.d_quant_wt.item()
-        qmax = abs(self.q_m_wt.item())
+    def _bit_width(self, which: str) -> int:
+        """round(log2(|q_m|^t / |d| + 1) + 1) of the `which` ("wt" / "act") quantizer (quant_layers.py:383-410)."""
+        d = getattr(self, f"d_quant_{which}").item()
+        qmax = abs(getattr(self, f"q_m_{which}").item())
         if self.quant_type == QuantizationType.SYMMETRIC_LINEAR:
             t = 1.0
         elif self.quant_type == QuantizationType.SYMMETRIC_NONLINEAR:
-            t = self.t_quant_wt.item()
+            t = getattr(self, f"t_quant_{which}").item()
         else:
             raise NotImplementedError
         return round(math.log2(math.exp(t * math.log(qmax)) / abs(d) + 1) + 1)
+
+    @property
+    def weight_bit(self) -> int:
+        return self._bit_width("wt")
 
     @property
     def activation_bit(self) -> int:
         if self.quant_mode != QuantizationMode.WEIGHT_AND_ACTIVATION:
             return 32
-        d = self.d_quant_act.item()
-        qmax = abs(self.q_m_act.item())
-        if self.quant_type == QuantizationType.SYMMETRIC_LINEAR:
-            t = 1.0
-        elif self.quant_type == QuantizationType.SYMMETRIC_NONLINEAR:
-            t = self.t_quant_act.item()
-        else:
-            raise NotImplementedError
-        return round(math.log2(math.exp(t * math.log(qmax)) / abs(d) + 1) + 1)
+        return self._bit_width("act")
 
     # -- MI355X state ---------------------------------------------------------------------------
     def prepare(self):
@@ -635,7 +615,7 @@ class QuantizeMixin:
                                  "device (the HIP path has no CPU fallback)")
         qt = _qtype_code(self.quant_type)
         n, k = w2.shape
-        npad, kpad = _round_up(n, _lib.TILE_N), _round_up(k, _lib.TILE_K)
+        npad, kpad = _lib.round_up(n, _lib.TILE_N), _lib.round_up(k, _lib.TILE_K)
         d_wt = _as_param_ptr(self.d_quant_wt, dev)
         qm_wt = _as_param_ptr(self.q_m_wt, dev)
         t_wt = _as_param_ptr(getattr(self, "t_quant_wt", None), dev)
@@ -665,10 +645,8 @@ class QuantizeMixin:
                 raise ValueError(f"{type(self).__name__}: loaded weight code {cmax} exceeds the quantizer's "
                                  f"saturation level {lw}")
             plan.extra["weight_codes"] = True
-            # packing integer values with the linear quantizer at d = 1 reproduces them exactly
             w32 = codes.to(device=dev, dtype=torch.float32).contiguous()
-            qt_pack, d_pack = _lib.QT_LINEAR, torch.ones(1, device=dev)
-            qm_pack, t_pack = torch.full((1,), 1024.0, device=dev), None
+            qt_pack, d_pack, qm_pack, t_pack = _lib.code_quantizer(dev)
         else:
             qt_pack, d_pack, qm_pack, t_pack = qt, d_wt, qm_wt, t_wt
         if act_ok and abs(lw) <= 127:
@@ -747,16 +725,8 @@ class QuantizeMixin:
     def _wonly_rows(self, x2: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
         """[M, k] fp32 rows (or rows already zero-padded to kpad columns) @ quantize_weight(W)^T + b on
         qvit_gemm_wonly (weight-only / wide-level plans)."""
-        M = x2.shape[0]
-        if (x2.dtype != torch.float32 or x2.stride(-1) != 1 or x2.shape[1] < plan.kpad or x2.stride(0) % 4
-                or x2.data_ptr() % 16):
-            xp = torch.zeros((M, plan.kpad), dtype=torch.float32, device=x2.device)
-            xp[:, :plan.k] = x2[:, :plan.k]
-            x2 = xp
-        ldy = _round_up(plan.n, 4)
-        y = torch.empty((M, ldy), dtype=torch.float32, device=x2.device)
-        _lib.gemm_wonly(x2, M, plan.kpad, plan.packed, plan.wfmt, plan.n, plan.npad, plan.d_wt, plan.bias_pad, y)
-        return y if ldy == plan.n else y[:, :plan.n]
+        return _lib.gemm_wonly_rows(x2, plan.k, plan.kpad, plan.packed, plan.wfmt, plan.n, plan.npad, plan.d_wt,
+                                    plan.bias_pad)
 
     def w_fakequant(self, plan: QuantPlan) -> torch.Tensor:
         """The reference's quantize_weight(W) (quant_layers.py:332-354), cached on the plan: d_w * k of the plan's
@@ -804,17 +774,11 @@ class QuantizeMixin:
     def _dgrad_hip(self, plan: QuantPlan, G2: torch.Tensor) -> torch.Tensor:
         """G2 @ (d_wt k_w), contiguous [M, k]: qvit_gemm_wonly on the transposed codes (rows = in-features,
         reduction = out-features)."""
-        M = G2.shape[0]
         packed_t, npad_t, kpad_t = plan.packed_t()
-        Gp = G2
-        if G2.shape[1] != kpad_t or G2.stride(0) % 4 or G2.data_ptr() % 16:
-            Gp = torch.zeros((M, kpad_t), dtype=torch.float32, device=G2.device)
-            Gp[:, :plan.n] = G2
-        ldy = _round_up(plan.k, 4)
-        y = torch.empty((M, ldy), dtype=torch.float32, device=G2.device)
-        if M:
-            _lib.gemm_wonly(Gp, M, kpad_t, packed_t, plan.wfmt, plan.k, npad_t, plan.d_wt, None, y)
-        return y if ldy == plan.k else y[:, :plan.k].contiguous()
+        if G2.shape[0] == 0:
+            return torch.empty((0, plan.k), dtype=torch.float32, device=G2.device)
+        return _lib.gemm_wonly_rows(G2, plan.n, kpad_t, packed_t, plan.wfmt, plan.k, npad_t, plan.d_wt,
+                                    None).contiguous()
 
     def _backward_plan(self, plan: QuantPlan, x: torch.Tensor, weight: torch.Tensor, G: torch.Tensor,
                        needs: tuple) -> tuple:
@@ -909,13 +873,13 @@ class QuantizeMixin:
         if epilogue in (_lib.EPI_I8, _lib.EPI_I8_GELU):
             nplan = next_layer.quant_plan()
             if out is None:
-                out = torch.empty((M, _round_up(plan.n, 16)), dtype=torch.int8, device=dev)
+                out = torch.empty((M, _lib.round_up(plan.n, 16)), dtype=torch.int8, device=dev)
             out_q, table = nplan.act_q, epilogue_table(nplan, epilogue)
         elif epilogue == _lib.EPI_I32:
             if out is None:
-                out = torch.empty((M, _round_up(plan.n, 4)), dtype=torch.int32, device=dev)
+                out = torch.empty((M, _lib.round_up(plan.n, 4)), dtype=torch.int32, device=dev)
         elif out is None:
-            out = torch.empty((M, _round_up(plan.n, 4)), dtype=torch.float32, device=dev)
+            out = torch.empty((M, _lib.round_up(plan.n, 4)), dtype=torch.float32, device=dev)
         wimg, wfmt = plan.gemm_weights()
         _lib.gemm(codes, M, plan.kpad, wimg, wfmt, plan.n, plan.npad, plan.d_act, plan.d_wt,
                   plan.bias_pad, epilogue, out, *out_q, epi_table=table)

@@ -58,9 +58,7 @@ def _check_gpu(x: torch.Tensor, what: str) -> None:
 ULTRA_BWD = os.environ.get("QVIT_ULTRA_BWD", "hip")
 ULTRA_BWD_DEFAULT_TORCH = ("wgrad",)
 DGRAD_HIP_MAX_PIXELS = 64 * 64
-_ULTRA_BWD_OPS = {"hip": ("dgrad", "wgrad"), "torch": (), "dgrad": ("dgrad",), "wgrad": ("wgrad",)}
-if ULTRA_BWD not in _ULTRA_BWD_OPS:
-    raise ValueError(f"QVIT_ULTRA_BWD={ULTRA_BWD!r}: expected hip, torch, dgrad or wgrad")
+_lib.backward_ops(ULTRA_BWD, "QVIT_ULTRA_BWD")   # an unknown value stops the import
 
 
 # "1": UltraNetQua.forward_modules routes BatchNorm2d (batch statistics) -> activation_quantize_fn -> MaxPool2d(2, 2)
@@ -78,10 +76,7 @@ def train_fuse_enabled() -> bool:
 
 
 def _backward_gemm_ops() -> tuple:
-    try:
-        ops = _ULTRA_BWD_OPS[ULTRA_BWD]
-    except KeyError:
-        raise ValueError(f"ULTRA_BWD = {ULTRA_BWD!r}: expected hip, torch, dgrad or wgrad") from None
+    ops = _lib.backward_ops(ULTRA_BWD, "ULTRA_BWD")
     return tuple(o for o in ops if o not in ULTRA_BWD_DEFAULT_TORCH) if ULTRA_BWD == "hip" else ops
 
 
@@ -202,16 +197,12 @@ def bn_act_pool(x: torch.Tensor, bn, act, pool=None):
     return _BnActPoolFunction.apply(xc, bn.weight, bn.bias, mean, invstd, 2 ** act.a_bit - 1, pool is not None)
 
 
-def _round_up(v: int, m: int) -> int:
-    return (v + m - 1) // m * m
-
-
 def weight_codes(weight: torch.Tensor, w_bit: int, kpad: int = None, cout_pad: int = None) -> torch.Tensor:
     """Integer weight codes of weight_quantize_fn (HIP), [cout_pad][kpad] in K order (ky, kx, c)."""
     _check_gpu(weight, "weight")
     w4 = weight if weight.dim() == 4 else weight.reshape(weight.shape[0], -1, 1, 1)
     cout, cin, ks, _ = w4.shape
-    kpad = kpad or _round_up(ks * ks * cin, 16)
+    kpad = kpad or _lib.round_up(ks * ks * cin, 16)
     cout_pad = cout_pad or cout
     return _lib.ultra_weight_codes(w4, w_bit, kpad, cout_pad)
 
@@ -220,7 +211,7 @@ def _weight_values(x: torch.Tensor, w_bit: int) -> torch.Tensor:
     """The fake-quant weight round(.) / n (:20) of the HIP quantizer, divided on the device as IEEE fp32."""
     w4 = x if x.dim() == 4 else x.reshape(x.shape[0], -1, 1, 1)
     cout, cin, ks, _ = w4.shape
-    _, vals = _lib.ultra_weight_codes(w4, w_bit, _round_up(ks * ks * cin, 16), cout, values=True)
+    _, vals = _lib.ultra_weight_codes(w4, w_bit, _lib.round_up(ks * ks * cin, 16), cout, values=True)
     return vals.reshape(x.shape)
 
 
@@ -281,15 +272,13 @@ class _PackedCodes:
         w4 = weight.detach() if weight.dim() == 4 else weight.detach().reshape(weight.shape[0], -1, 1, 1)
         cout, cin, kh, kw = w4.shape
         k = cin * kh * kw
-        self.n, self.npad, self.kpad = cout, _round_up(cout, _lib.TILE_N), _round_up(k, _lib.TILE_K)
-        codes = _lib.ultra_weight_codes(w4, w_bit, _round_up(k, 16), cout)       # (ky, kx, c) order
+        self.n, self.npad, self.kpad = cout, _lib.round_up(cout, _lib.TILE_N), _lib.round_up(k, _lib.TILE_K)
+        codes = _lib.ultra_weight_codes(w4, w_bit, _lib.round_up(k, 16), cout)       # (ky, kx, c) order
         codes = codes[:, :k].view(cout, kh, kw, cin).permute(0, 3, 1, 2).reshape(cout, k).float().contiguous()
         n_lvl = 2 ** (w_bit - 1) - 1
         dev = weight.device
         self.wfmt = _lib.W4 if n_lvl <= 7 else _lib.W8
-        ovf = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.packed = _lib.pack_weight(codes, _lib.QT_LINEAR, torch.ones(1, device=dev),
-                                       torch.full((1,), 1024.0, device=dev), None, self.wfmt, self.npad, self.kpad, ovf)
+        self.packed = _lib.pack_codes(codes, self.wfmt, self.npad, self.kpad)
         self.d_wt = torch.full((1,), 1.0 / n_lvl, dtype=torch.float32, device=dev)
         self.bias_pad = _lib.pad_bias(bias, cout, self.npad, dev)
         self._shape4, self._w_bit, self._packed_t = (cout, cin, kh, kw), w_bit, None
@@ -308,13 +297,10 @@ class _PackedCodes:
             cout, cin, kh, kw = self._shape4
             k = cin * kh * kw
             codes = _lib.ultra_weight_codes(weight.detach().reshape(cout, cin, kh, kw), self._w_bit,
-                                            _round_up(k, 16), cout)       # (ky, kx, c) order, as get()
+                                            _lib.round_up(k, 16), cout)       # (ky, kx, c) order, as get()
             ct = codes[:, :k].view(cout, kh, kw, cin).float().flip(1, 2).permute(3, 0, 1, 2).reshape(cin, cout * kh * kw)
-            npad_t, kpad_t = _round_up(cin, _lib.TILE_N), _round_up(cout * kh * kw, _lib.TILE_K)
-            dev = ct.device
-            ovf = torch.zeros(1, dtype=torch.int32, device=dev)
-            img = _lib.pack_weight(ct.contiguous(), _lib.QT_LINEAR, torch.ones(1, device=dev),
-                                   torch.full((1,), 1024.0, device=dev), None, self.wfmt, npad_t, kpad_t, ovf)
+            npad_t, kpad_t = _lib.round_up(cin, _lib.TILE_N), _lib.round_up(cout * kh * kw, _lib.TILE_K)
+            img = _lib.pack_codes(ct.contiguous(), self.wfmt, npad_t, kpad_t)
             self._packed_t = (img, cin, npad_t, kpad_t)
         return self._packed_t
 
@@ -385,16 +371,8 @@ class _ConvQFunction(torch.autograd.Function):
 
 def _linear_codes_forward(module, input: torch.Tensor) -> torch.Tensor:
     c = module._codes.get(module.weight, module.bias, module.w_bit)
-    x2 = input.detach().reshape(-1, module.in_features)
-    if (x2.dtype != torch.float32 or x2.stride(-1) != 1 or c.kpad != module.in_features or x2.stride(0) % 4
-            or x2.data_ptr() % 16):
-        xp = torch.zeros((x2.shape[0], c.kpad), dtype=torch.float32, device=x2.device)
-        xp[:, :module.in_features] = x2
-        x2 = xp
-    ldy = _round_up(c.n, 4)
-    y = torch.empty((x2.shape[0], ldy), dtype=torch.float32, device=x2.device)
-    _lib.gemm_wonly(x2, x2.shape[0], c.kpad, c.packed, c.wfmt, c.n, c.npad, c.d_wt, c.bias_pad, y)
-    y = y if ldy == c.n else y[:, :c.n]
+    y = _lib.gemm_wonly_rows(input.detach().reshape(-1, module.in_features), module.in_features, c.kpad, c.packed,
+                             c.wfmt, c.n, c.npad, c.d_wt, c.bias_pad)
     return y.reshape(*input.shape[:-1], c.n)
 
 
@@ -423,14 +401,7 @@ class _LinearQFunction(torch.autograd.Function):
             if "dgrad" in _backward_gemm_ops() and M:
                 c = mod._codes.get(weight, mod.bias, mod.w_bit)
                 img, rows, npad_t, kpad_t = c.packed_t(weight)
-                Gp = G2
-                if G2.shape[1] != kpad_t or G2.data_ptr() % 16:
-                    Gp = torch.zeros((M, kpad_t), dtype=torch.float32, device=G2.device)
-                    Gp[:, :mod.out_features] = G2
-                ldy = _round_up(rows, 4)
-                y = torch.empty((M, ldy), dtype=torch.float32, device=G2.device)
-                _lib.gemm_wonly(Gp, M, kpad_t, img, c.wfmt, rows, npad_t, c.d_wt, None, y)
-                gx2 = y if ldy == rows else y[:, :rows]
+                gx2 = _lib.gemm_wonly_rows(G2, mod.out_features, kpad_t, img, c.wfmt, rows, npad_t, c.d_wt, None)
             else:
                 gx2 = torch.mm(G2, _weight_values(weight, mod.w_bit))
             grad_x = gx2.reshape(input.shape).to(input.dtype)

@@ -48,10 +48,6 @@ def bn_act_quantize_int(gamma, beta, mean, var, eps, w_bit: int, in_bit: int, ou
     return inc_q, bias_q
 
 
-def _round_up(v: int, m: int) -> int:
-    return (v + m - 1) // m * m
-
-
 class UltraNetIntDeploy:
     """Integer-parameter UltraNet on the GPU, built from a generate_params npz (path or dict of arrays)."""
 
@@ -97,8 +93,8 @@ class UltraNetIntDeploy:
 
     def _k_order(self, codes: np.ndarray, cin: int, cout: int, ks: int) -> torch.Tensor:
         kdim = ks * ks * cin
-        kpad = _round_up(kdim, 64)
-        out = np.zeros((_round_up(cout, 16), kpad), dtype=np.int8)
+        kpad = _lib.round_up(kdim, 64)
+        out = np.zeros((_lib.round_up(cout, 16), kpad), dtype=np.int8)
         out[:cout, :kdim] = codes.transpose(0, 2, 3, 1).reshape(cout, kdim)   # (ky, kx, c)
         return torch.from_numpy(out).to(self.device)
 

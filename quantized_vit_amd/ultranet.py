@@ -111,10 +111,6 @@ def _aten_batch_norm():
         torch.backends.cudnn.enabled = prev
 
 
-def _round_up(v, m):
-    return (v + m - 1) // m * m
-
-
 class UltraNetQua(nn.Module):
     """mymodel.py:62-144."""
 
@@ -170,7 +166,7 @@ class UltraNetQua(nn.Module):
             if k == 0:   # float-input layer: the fake-quant weight values feed a direct fp32 conv
                 _, codes = _lib.ultra_weight_codes(conv.weight, W_BIT, 32, 16, values=True)
             else:
-                codes = _lib.ultra_weight_codes(conv.weight, W_BIT, _round_up(9 * cin, 64), _round_up(cout, 16))
+                codes = _lib.ultra_weight_codes(conv.weight, W_BIT, _lib.round_up(9 * cin, 64), _lib.round_up(cout, 16))
             alpha, shift = _lib.ultra_bn_fold(bn, dev)
             plan.append((codes, alpha, shift, cout, pool is not None))
         hcodes = _lib.ultra_weight_codes(head.weight, W_BIT, 64, 48)
