@@ -28,6 +28,10 @@
  *                             OTO/optimizer/geta.py:167-248, :281-521, :944-1026 and base_hybrid_sparse_optimizer.py:
  *                             194-291: the saliency scores and the joint pruning and quantization stage for declared
  *                             row groups, a fixed number of launches per step and no .item().
+ *   qvit_train_loss           QViT_with_GETA/utils.py:120-154 (one_hot, cross_entropy_onehot_target, mixup_func on the
+ *                             targets), :261-262 (the correct count) and :264-280 (CE, the distillation KL and their
+ *                             blend) of train_one_epoch, and evaluate's CrossEntropyLoss (:350-354): the objective,
+ *                             its gradient with respect to the logits and the accuracy count in two launches.
  *   qvit_pack_weight          quant_layers.py:332-354 (QuantizeMixin.quantize_weight) + the GEMM operand
  *                             layout: codes packed int4 (8 per u32) or int8, rows padded/permuted.
  *   qvit_im2col_quant_i8      quant_layers.py:575-587 (QuantizeConv2d.forward): the conv input patches
@@ -237,6 +241,47 @@ int64_t qvit_quant_error_workspace_bytes(int64_t rows, int64_t cols, int ncand);
 int qvit_quant_error(const float* x, int64_t rows, int64_t cols, int64_t ldx, int qtype, const float* d,
                      const float* q_m, const float* t, int ncand, int accumulate, double* err, int64_t* nclip,
                      void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/*
+ * The training objective of QViT_with_GETA/utils.py (train_one_epoch :197-325, evaluate :328-366) over a batch of
+ * logits, with its gradient and the accuracy count, in two launches and without a [B, C] temporary:
+ *   y[c]     = v0 + (v1 - v0) (gamma [c == label_a] + (1 - gamma) [c == label_b]), v0 = eps / C, v1 = 1 - eps + v0
+ *              (one_hot :120-130 followed by mixup_func's targets.mul_(gamma).add_(1 - gamma, perm_target) :153);
+ *   ce_row   = lse(s) - sum_c y[c] s[c]                       (cross_entropy_onehot_target :133-139)
+ *   kd_row   = sum_c p_t[c] (log p_t[c] - log_softmax(s / T)[c]), p_t = softmax(t / T)    (F.kl_div :272-274)
+ *   out[0]   = (1 - kd_alpha) out[1] + kd_alpha out[2] with a teacher and kd_alpha > 0 (:278), else out[1] (:280)
+ *   out[1]   = mean of ce_row;  out[2] = mean of kd_row times T^2 ('batchmean', :274; 0 without a teacher)
+ *   out[3]   = number of rows whose argmax is label_a (:261-262);  out[4] = rows with a label outside [0, C)
+ *   dlogits[r][c] = d out[0] / d logits[r][c]
+ *                 = (1 - kd_alpha) / B (softmax(s)[c] - y[c]) + kd_alpha T / B (softmax(s / T)[c] - p_t[c]),
+ *              the first term alone at weight 1 / B without a teacher or with kd_alpha == 0.
+ *   logits   : fp32 [B][lds], C <= lds; columns >= C are never read. teacher: the same with ldt, or NULL.
+ *   label_a  : int64 [B], the hard labels. label_b: int64 [B], the mixup partners (labels[perm]), or NULL: then
+ *              gamma is not used and the target is the smoothed one-hot of label_a. eps == 0 and label_b NULL is
+ *              torch.nn.CrossEntropyLoss() (evaluate's form). gamma, eps, kd_alpha and T are host values.
+ *   dlogits  : fp32 [B][ldg], or NULL for the no-gradient form: the same reads and reductions, no gradient pass,
+ *              the same bits in out.
+ *   out      : float[5]. workspace: qvit_train_loss_workspace_bytes(B) bytes (32 per row), 8-byte aligned.
+ * One workgroup owns a row. A row of at most 4096 classes stays in registers and is read once; a longer one is read
+ * twice (an online pass for the reductions, one for the gradient). 16-byte accesses when logits, teacher and dlogits
+ * are 16-byte aligned with strides % 4 == 0, else 4-byte accesses with the same element-to-thread map: the same bits.
+ * The maxima are subtracted before every exp. Per-row results are finished in double and folded in row order, in
+ * double, by a second launch of one workgroup; no atomics, so two identical calls give identical bits.
+ * The argmax is the lowest index attaining the maximum, -0 equal to +0 and a NaN above every number (torch.max).
+ * A label outside [0, C) indexes nothing: it matches no class (its part of y is dropped), its row counts as
+ * incorrect and is counted in out[4].
+ * Order of the checks (part of the ABI): logits, label_a, out or workspace NULL (QVIT_ENULL); B < 0, B > 2^24, C < 1
+ * or C > 2^30 (QVIT_EINVAL); lds < C, or ldt < C with a teacher, or ldg < C with dlogits (QVIT_EINVAL); T not finite
+ * or not positive (QVIT_EINVAL); eps, gamma or kd_alpha outside [0, 1] (QVIT_EINVAL); a short workspace
+ * (QVIT_EINVAL); alignment (logits, teacher, dlogits, out 4 bytes; labels and workspace 8: QVIT_EALIGN). B == 0
+ * returns QVIT_OK without a launch and leaves out as it is. qvit_train_loss_workspace_bytes returns QVIT_EINVAL for
+ * B < 0 or B > 2^24.
+ */
+int64_t qvit_train_loss_workspace_bytes(int64_t B);
+int qvit_train_loss(const float* logits, int64_t B, int64_t C, int64_t lds, const float* teacher, int64_t ldt,
+                    const int64_t* label_a, const int64_t* label_b, float gamma, float eps, float kd_alpha, float T,
+                    float* dlogits, int64_t ldg, float* out /* [5] */, void* workspace, int64_t workspace_bytes,
+                    hipStream_t stream);
 
 /*
  * The quantization-aware stages of the GETA optimizer (optimizer/geta.py:571-804, :873-943 with the pruning stages

@@ -30,6 +30,7 @@ from .calibrate import (
 from .qat_optim import QuantAwareOptimizer
 from .qat_prune import PruneGroup, vit_head_prune_groups, vit_mlp_prune_groups
 from .compress import compress_pruned_heads, compress_pruned_mlp
+from .losses import TrainLoss, TrainLossResult, mixup
 
 __all__ = [
     "LAYER_TO_QUANTLAYER", "NanInGradientError", "QuantizationMode", "QuantizationType", "QuantizeConv2d",
@@ -37,5 +38,5 @@ __all__ = [
     "model_to_quantize_model", "QuantChoice", "apply_quant_choices", "build_quantized_vit", "clip_candidates",
     "collect_input_absmax", "quantize_pretrained", "search_activation_quant", "search_weight_quant",
     "set_activation_quant", "QuantAwareOptimizer", "PruneGroup", "vit_mlp_prune_groups", "compress_pruned_mlp",
-    "vit_head_prune_groups", "compress_pruned_heads",
+    "vit_head_prune_groups", "compress_pruned_heads", "TrainLoss", "TrainLossResult", "mixup",
 ]

@@ -133,6 +133,8 @@ _SIGNATURES = {
     "qvit_fake_quant_f32": [_c_p, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
     "qvit_quant_backward": [_c_p, _c_p, _i64, _i32, _c_p, _c_p, _c_p, _f32, _f32, _f32, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_quant_error": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _i32, _c_p, _c_p, _c_p, _i64, _c_p],
+    "qvit_train_loss": [_c_p, _i64, _i64, _i64, _c_p, _i64, _c_p, _c_p, _f32, _f32, _f32, _f32, _c_p, _i64, _c_p, _c_p,
+                        _i64, _c_p],
     "qvit_qat_step": [_c_p, _i32, _c_p, _i64, _i32, _i32] + [_f32] * 11 + [_c_p],
     "qvit_qat_quant_step": [_c_p, _i32, _c_p, _i32, _i32, _i32, _i32] + [_f32] * 11 + [_i32] * 4 + [_c_p],
     "qvit_prune_scores": [_c_p, _i32, _c_p, _i32, _c_p, _i64, _c_p, _i32, _i32] + [_f32] * 11 + [_c_p],
@@ -217,6 +219,7 @@ _SIGNATURES = {
 INT64_FUNCS = {
     "qvit_quant_backward_workspace_bytes": [_i64],
     "qvit_quant_error_workspace_bytes": [_i64, _i64, _i32],
+    "qvit_train_loss_workspace_bytes": [_i64],
     "qvit_layernorm_quant_backward_workspace_bytes": [_i64, _i64],
     "qvit_gelu_quant_backward_workspace_bytes": [_i64],
     "qvit_attention_backward_workspace_bytes": [_i64, _i64, _i64],
@@ -398,6 +401,64 @@ def quant_error(x2d: torch.Tensor, qtype: int, d: torch.Tensor, q_m: torch.Tenso
                                 ncand, int(bool(accumulate)), _ptr(err), _ptr(nclip), _ptr(ws),
                                 ws.numel() * ws.element_size(), _stream(dev)), "qvit_quant_error")
     return err, nclip
+
+
+def _loss_rows(t: torch.Tensor, name: str, shape=None) -> int:
+    """The row stride of a [B, C] fp32 logits tensor for qvit_train_loss (unit column stride, any row stride)."""
+    _require_gpu(t, name)
+    if t.dtype != torch.float32:
+        raise QvitError(f"train_loss: {name} must be float32 (got dtype {t.dtype})")
+    if t.dim() != 2 or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise QvitError(f"train_loss: {name} must be a [B, C] matrix" + (f" of shape {tuple(shape)}" if shape else "")
+                        + f" (got shape {tuple(t.shape)})")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise QvitError(f"train_loss: {name} must have unit column stride (got strides {tuple(t.stride())})")
+    rows, cols = t.shape
+    ld = t.stride(0) if rows > 1 else max(cols, t.stride(0))
+    if ld < cols:
+        raise QvitError(f"train_loss: the rows of {name} overlap (row stride {ld} for {cols} columns)")
+    return ld
+
+
+def _loss_labels(v: torch.Tensor, name: str, rows: int, dev) -> torch.Tensor:
+    if not isinstance(v, torch.Tensor) or v.dtype != torch.int64:
+        raise QvitError(f"train_loss: {name} must be an int64 tensor (got {getattr(v, 'dtype', type(v))})")
+    if v.device != dev:
+        raise QvitError(f"train_loss: {name} must be on the logits' device {dev} (got device {v.device})")
+    if v.dim() != 1 or v.numel() != rows:
+        raise QvitError(f"train_loss: {name} must hold one label per row, shape ({rows},) (got shape "
+                        f"{tuple(v.shape)})")
+    return v.contiguous()
+
+
+def train_loss(logits: torch.Tensor, labels: torch.Tensor, teacher: Optional[torch.Tensor] = None,
+               labels_b: Optional[torch.Tensor] = None, gamma: float = 1.0, eps: float = 0.0, kd_alpha: float = 0.0,
+               temperature: float = 1.0, want_grad: bool = True):
+    """The reference's training objective over fp32 logits [B, C] (qvit_train_loss): soft-target cross-entropy
+    against the smoothed (eps), mixed-up (labels_b, gamma) one-hot of `labels`, the distillation KL against `teacher`
+    at `temperature`, their blend at `kd_alpha`, and the accuracy count. Returns (out, dlogits): out float32 [5] =
+    (loss, mean CE, KD, correct rows, rows with a label outside [0, C)) and dlogits = d loss / d logits, contiguous
+    [B, C] (None unless want_grad), all on the device with no host sync."""
+    ld = _loss_rows(logits, "logits")
+    rows, cols = logits.shape
+    dev = logits.device
+    if cols < 1:
+        raise QvitError(f"train_loss: logits must have at least one class (got shape {tuple(logits.shape)})")
+    ldt = _loss_rows(teacher, "teacher_logits", logits.shape) if teacher is not None else 0
+    if teacher is not None and teacher.device != dev:
+        raise QvitError(f"train_loss: teacher_logits must be on the logits' device {dev} (got {teacher.device})")
+    la = _loss_labels(labels, "labels", rows, dev)
+    lb = _loss_labels(labels_b, "the mixup labels", rows, dev) if labels_b is not None else None
+    grad = torch.empty((rows, cols), dtype=torch.float32, device=dev) if want_grad else None
+    if rows == 0:   # (the entry point launches nothing for an empty batch and leaves out as it is)
+        return torch.zeros(5, dtype=torch.float32, device=dev), grad
+    out = torch.empty(5, dtype=torch.float32, device=dev)
+    lib = load()
+    ws = _workspace(int(lib.qvit_train_loss_workspace_bytes(rows)), "qvit_train_loss_workspace_bytes", None, dev)
+    _check(lib.qvit_train_loss(_ptr(logits), rows, cols, ld, _ptr(teacher), ldt, _ptr(la), _ptr(lb), float(gamma),
+                               float(eps), float(kd_alpha), float(temperature), _ptr(grad), cols, _ptr(out), _ptr(ws),
+                               ws.numel() * ws.element_size(), _stream(dev)), "qvit_train_loss")
+    return out, grad
 
 
 def qat_step(tensors: torch.Tensor, ntensors: int, chunks: torch.Tensor, nchunks: int, hyper: tuple) -> None:

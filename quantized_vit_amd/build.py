@@ -22,7 +22,7 @@ ARCH = "gfx950"
 SOURCES = ["quant_kernels.hip", "quant_backward.hip", "train_fuse.hip", "gemm_w4a8.hip", "gemm_ws.hip",
            "gemm_wonly.hip", "gemm_wgrad.hip", "attention.hip", "attention_backward.hip", "qkv_attention.hip",
            "ultra_conv.hip", "ultra_backward.hip", "ultra_bn_fuse.hip", "conv_backward.hip", "u8_input.hip",
-           "quant_error.hip", "qat_step.hip", "prune_step.hip"]
+           "quant_error.hip", "qat_step.hip", "prune_step.hip", "train_loss.hip"]
 # sources with inline-asm register loads: their device assembly is kept beside the objects (the very code in the
 # library) for tools/asm_load_check.py (tests/test_asm_loads.py)
 ASM_CHECKED = ["gemm_w4a8.hip", "ultra_conv.hip"]
@@ -40,6 +40,13 @@ HIPCC_FLAGS = [
     # keep IEEE fp32 division/sqrt: the quantizer's careful path depends on it
     "-fhip-fp32-correctly-rounded-divide-sqrt",
 ]
+# flags of single sources, after the common ones. train_loss.hip: scalar fp32 arithmetic only (no packed
+# v_pk_*_f32 forms from the vectoriser: the kernel is bound by its loads, and the scalar forms round as written)
+SOURCE_FLAGS = {"train_loss.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
+def source_flags(src: str) -> list:
+    return SOURCE_FLAGS.get(src, [])
 
 
 def _hipcc() -> str:
@@ -61,6 +68,7 @@ def source_digest(defines: tuple = ()) -> str:
         with open(p, "rb") as f:
             h.update(f.read())
     h.update(" ".join(HIPCC_FLAGS + [f"-D{d}" for d in defines]).encode())
+    h.update(repr(sorted(SOURCE_FLAGS.items())).encode())
     return h.hexdigest()
 
 
@@ -93,7 +101,8 @@ def build(force: bool = False, verbose: bool = False, defines: tuple = (), lib: 
 
     def compile_one(src: str) -> str:
         obj = os.path.join(build_dir, os.path.splitext(src)[0] + ".o")
-        cmd = [hipcc, *HIPCC_FLAGS, *dflags, "-I", INCLUDE, "-c", os.path.join(CSRC, src), "-o", obj]
+        cmd = [hipcc, *HIPCC_FLAGS, *source_flags(src), *dflags, "-I", INCLUDE, "-c", os.path.join(CSRC, src), "-o",
+               obj]
         keep_asm = src in ASM_CHECKED and build_dir == BUILD
         if keep_asm:
             cmd.insert(1, "-save-temps=obj")

@@ -34,8 +34,8 @@ def main():
         if not os.path.exists(path):
             path = os.path.join(build.CSRC, src)
         obj = os.path.join(out_dir, os.path.splitext(src)[0] + ".o")
-        cmd = [hipcc, *build.HIPCC_FLAGS, *[f"-D{d}" for d in a.defines], "-I", a.csrc, "-I", build.INCLUDE,
-               "-c", path, "-o", obj]
+        cmd = [hipcc, *build.HIPCC_FLAGS, *build.source_flags(src), *[f"-D{d}" for d in a.defines], "-I", a.csrc,
+               "-I", build.INCLUDE, "-c", path, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode:
             raise SystemExit(f"{src}: {r.stderr}")
