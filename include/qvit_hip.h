@@ -28,7 +28,11 @@
  *                             OTO/optimizer/geta.py:167-248, :281-521, :944-1026 and base_hybrid_sparse_optimizer.py:
  *                             194-291: the saliency scores and the joint pruning and quantization stage for declared
  *                             row groups, a fixed number of launches per step and no .item().
- *   qvit_train_loss           QViT_with_GETA/utils.py:120-154 (one_hot, cross_entropy_onehot_target, mixup_func on the
+ *   qvit_group_lasso / qvit_group_lasso_scale
+ *                             QViT_with_GETA/utils.py:157-194 (compute_group_lasso_loss_from_geta, and what backward()
+ *                             makes of it) and base_hybrid_sparse_optimizer.py:293-333 (gl_scale): the group-lasso
+ *                             penalty over the same row groups, its gradient added into the members' gradients.
+ *   qvit_train_loss          QViT_with_GETA/utils.py:120-154 (one_hot, cross_entropy_onehot_target, mixup_func on the
  *                             targets), :261-262 (the correct count) and :264-280 (CE, the distillation KL and their
  *                             blend) of train_one_epoch, and evaluate's CrossEntropyLoss (:350-354): the objective,
  *                             its gradient with respect to the logits and the accuracy count in two launches.
@@ -439,6 +443,40 @@ int qvit_prune_joint_apply(const void* groups, int ngroups, const void* members,
                            float first_momentum, float second_momentum, float alpha1, float alpha2,
                            float weight_decay, float bias_correction1, float bias_correction2, float clip_lo,
                            float clip_hi, hipStream_t stream);
+
+/*
+ * The group-lasso penalty over the prunable row groups (QViT_with_GETA/utils.py:157-194) with its gradient, and the
+ * per-unit weights gl_scale (base_hybrid_sparse_optimizer.py:293-333). groups and members are the tables above; the
+ * penalty reads p, reads and writes the members' grad (through the table's const pointer) and touches neither m nor v.
+ *   units : nunits entries of 16 bytes { int32_t group, row, state, link; }, one per unit that takes part: row = the
+ *           unit's index in its group; link = where the unit is several rows, the index in `rows` of its first row,
+ *           else unused. The index u of a unit here is its index in scale, scores, sumsq and coef.
+ *   rows  : nrows entries, the physical rows of the units of several rows, a unit's rows contiguous, section-major
+ *           with its rows ascending: row = the physical row, link = the unit's index u. May be NULL when nrows == 0.
+ *
+ * qvit_group_lasso: sumsq[u] = sum p^2 over unit u in every member (double; a member without grad counts),
+ *   coef[u] = (float)(lambda scale[u] / sqrt(sumsq[u])), 0 where sumsq[u] == 0, grad = grad + coef[u] p (two fp32
+ *   roundings, not contracted) on every element of the unit in every member with a grad, skipped where coef[u] == 0,
+ *   so those gradients keep their bits; loss[0] = (float) sum_u scale[u] sqrt(sumsq[u]) in double. scale NULL: all 1.
+ *   sumsq is double[nunits + nrows]: the rows' sums follow the units'. A unit of one row is held in registers where
+ *   it needs at most QVIT_GROUP_LASSO_SLOTS slots, a slot being up to 256 elements of one member, and p is read once;
+ *   a larger one and the units of several rows read p twice. Sums are lane-strided, then the wave tree; a unit's rows
+ *   are added by one wave, lane l taking rows l, l + 64, .. of its listing; the loss by one workgroup, thread i taking
+ *   units i, i + 1024, ..: the same bits in every run, no atomics. A unit or row that disagrees with the tables gets zeros / is skipped.
+ *   Launches: 2, and 3 more when nrows > 0, whatever the groups.
+ * qvit_group_lasso_scale: inv_u = clamp(sqrt(max(elems_g, 1)) / max(|scores[u]|, 1e-8), 0.1, 10), 1 for a NaN score;
+ *   scale[u] = (float)(inv_u / max(mean_u inv_u, 1e-8)), in double, by one workgroup in a fixed order.
+ * Order of the checks (part of the ABI): a table or an output NULL, rows NULL with nrows > 0 (QVIT_ENULL; scale may be
+ * NULL); a table or sumsq off 8 bytes, scale, scores, coef or loss off 4 (QVIT_EALIGN); a count < 0, nunits or nrows >
+ * 2^31 - 1 (QVIT_EINVAL); lambda negative or not finite (QVIT_EINVAL); ngroups, nmembers or nunits zero is a no-op
+ * success.
+ */
+#define QVIT_GROUP_LASSO_SLOTS 8
+int qvit_group_lasso(const void* groups, int ngroups, const void* members, int nmembers, const void* units,
+                     int64_t nunits, const void* rows, int64_t nrows, const float* scale, double lambda, double* sumsq,
+                     float* coef, float* loss, hipStream_t stream);
+int qvit_group_lasso_scale(const void* groups, int ngroups, const void* units, int64_t nunits, const float* scores,
+                           float* scale, hipStream_t stream);
 
 /*
  * y = GELU(x) elementwise over n contiguous floats: nn.GELU() (QViT_with_GETA/vit_model.py:173,242), bit-identical

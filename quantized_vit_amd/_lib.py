@@ -56,6 +56,8 @@ PRUNE_GROUP_BYTES = 64    # the group, member and item descriptors of the qvit_p
 PRUNE_MEMBER_BYTES = 48
 PRUNE_ITEM_BYTES = 16
 PRUNE_IMPORTANT, PRUNE_REDUNDANT, PRUNE_PRUNED = 0, 1, 2
+GROUP_LASSO_SLOTS = 8          # QVIT_GROUP_LASSO_SLOTS: the slots of a one-row unit qvit_group_lasso holds in registers,
+GROUP_LASSO_SLOT_ELEMS = 256   # a slot being up to this many elements of one member
 
 # The descriptors as numpy dtypes: the Python statement of the structs' layouts (their fields, in their order; natural
 # alignment leaves no padding). The host tables are arrays of these and reach the device byte for byte.
@@ -144,6 +146,8 @@ _SIGNATURES = {
     "qvit_prune_joint_reduce": [_c_p, _i32, _c_p, _i32, _c_p, _i64, _c_p, _i32, _i32] + [_f32] * 11 + [_c_p],
     "qvit_prune_joint_finish": [_c_p, _i32, _c_p, _i64, _f64, _i32, _i32, _i32, _i32, _c_p, _c_p, _c_p],
     "qvit_prune_joint_apply": [_c_p, _i32, _c_p, _i32, _c_p, _i64, _c_p, _i32, _i32] + [_f32] * 11 + [_c_p],
+    "qvit_group_lasso": [_c_p, _i32, _c_p, _i32, _c_p, _i64, _c_p, _i64, _c_p, _f64, _c_p, _c_p, _c_p, _c_p],
+    "qvit_group_lasso_scale": [_c_p, _i32, _c_p, _i64, _c_p, _c_p, _c_p],
     "qvit_gelu_f32": [_c_p, _i64, _c_p, _c_p],
     "qvit_layernorm_quant_backward": [_c_p, _i64, _i64, _i64, _c_p, _c_p, _f32, _i32, _c_p, _c_p, _c_p, _f32, _f32,
                                       _c_p, _i64, _c_p, _i64, _c_p, _c_p, _c_p, _c_p, _i64, _c_p],
@@ -538,6 +542,31 @@ def prune_joint_apply(groups: torch.Tensor, ngroups: int, members: torch.Tensor,
     assert gamma.dtype == torch.float32 and gamma.numel() >= ngroups
     _check(load().qvit_prune_joint_apply(_ptr(groups), ngroups, _ptr(members), nmembers, _ptr(items), nitems,
                                          _ptr(gamma), *hyper, _stream(groups.device)), "qvit_prune_joint_apply")
+
+
+def group_lasso(groups: torch.Tensor, ngroups: int, members: torch.Tensor, nmembers: int, units: torch.Tensor,
+                nunits: int, rows: Optional[torch.Tensor], nrows: int, scale: Optional[torch.Tensor], lam: float,
+                sumsq: torch.Tensor, coef: torch.Tensor, loss: torch.Tensor) -> None:
+    """The group-lasso penalty and its gradient over the listed units (qvit_group_lasso): `sumsq` float64
+    [nunits + nrows], `coef` float32 [nunits] and `loss` float32 [1] are written, the members' gradients updated in
+    place. `scale` None: every unit weighs 1."""
+    _require_gpu(groups, "group table")
+    assert sumsq.dtype == torch.float64 and sumsq.numel() >= nunits + nrows and coef.dtype == torch.float32 and \
+        coef.numel() >= nunits and loss.dtype == torch.float32 and loss.numel() >= 1
+    assert scale is None or (scale.dtype == torch.float32 and scale.numel() >= nunits)
+    _check(load().qvit_group_lasso(_ptr(groups), ngroups, _ptr(members), nmembers, _ptr(units), nunits, _ptr(rows),
+                                   nrows, _ptr(scale), float(lam), _ptr(sumsq), _ptr(coef), _ptr(loss),
+                                   _stream(groups.device)), "qvit_group_lasso")
+
+
+def group_lasso_scale(groups: torch.Tensor, ngroups: int, units: torch.Tensor, nunits: int, scores: torch.Tensor,
+                      scale: torch.Tensor) -> None:
+    """gl_scale of every listed unit from its saliency score (qvit_group_lasso_scale)."""
+    _require_gpu(groups, "group table")
+    assert scores.dtype == torch.float32 and scores.numel() >= nunits and scale.dtype == torch.float32 and \
+        scale.numel() >= nunits
+    _check(load().qvit_group_lasso_scale(_ptr(groups), ngroups, _ptr(units), nunits, _ptr(scores), _ptr(scale),
+                                         _stream(groups.device)), "qvit_group_lasso_scale")
 
 
 def gelu_f32(x: torch.Tensor) -> torch.Tensor:

@@ -26,42 +26,14 @@
 // the dense step runs, so no grad_variant tensor exists and a member row outside the redundant set gets the bits
 // qvit_qat_step would give it (minus adamw's decay in the joint branch, as in the reference). Sums are double, in a
 // fixed order: lane-strided accumulation, the wave tree, then (joint finish) partials folded in index order.
+#include "prune_common.h"
 #include "qat_common.h"
 
 namespace {
 
 constexpr int kLoopCap = 861;   // ceil(ln(FLT_MAX / FLT_TRUE_MIN) / ln(1.25)): x 1.25 per turn crosses fp32's range
 
-struct PruneMember {    // 48 B
-  float* p;
-  const float* grad;    // NULL: no update (pruned rows are still zeroed), no part in the sums
-  float* m;
-  float* v;
-  int64_t width;        // elements per row
-  int32_t quantized;    // 1: the group's layer's weight (clip, res and quantize by its weight quantizer)
-  int32_t flags;        // bit 0: this tensor's first step
-};
-struct PruneGroup {     // 64 B
-  float* d;             // weight quantizer scalars of the group's layer; t NULL: the linear type
-  const float* qm;
-  const float* t;
-  int32_t member_begin, member_count;
-  int32_t rows;
-  int32_t joint;        // 1: the joint stage (active redundant rows); 0: the stage path
-  int32_t red_begin, red_count;   // its redundant rows' partials
-  int64_t elems;        // elements per unit over all members
-  int32_t sections, unit_rows;    // 0 as 1; both 1: a unit is one row
-};
-struct PruneItem {      // 16 B
-  int32_t group, row;
-  int32_t state;        // 0 important, 1 active redundant, 2 pruned
-  int32_t link;         // a row item: the row's unit (0 where a unit is one row); a unit entry of the fold (row = the
-                        // unit): the index in the row items of row 0 of its group
-};
-enum { kImportant = 0, kRedundant = 1, kPruned = 2 };
-QVIT_DEV int64_t rows_per_unit(const PruneGroup& G) {
-  return (int64_t)(G.sections > 1 ? G.sections : 1) * (G.unit_rows > 1 ? G.unit_rows : 1);
-}
+enum { kImportant = 0, kRedundant = 1, kPruned = 2 };   // PruneItem.state
 
 // the weight quantizer as geta.py:806-850 states it: range_pow has no 1e-6 (the layers' forward has one)
 struct WeightQuant {
@@ -96,10 +68,6 @@ QVIT_DEV void clip_res(float x, const WeightQuant& w, float& clip, float& res) {
 // _quantize_helper (:806-819) of one element: d * code, by qvit_common.h's careful sequence
 QVIT_DEV float quantize_weight(float x, const WeightQuant& w) {
   return w.qp.d * quant_code_from_pow(x, pow_abs(fabsf(x), w), w.qp);
-}
-
-QVIT_DEV bool member_vec(const PruneMember& t) {
-  return ((((uintptr_t)t.p | (uintptr_t)t.grad | (uintptr_t)t.m | (uintptr_t)t.v) & 15) == 0) && (t.width & 3) == 0;
 }
 
 // Walks row `row` of member t: f(i, p, g, m, v) per element with m, v loaded (0 when fresh or absent); f returns the
@@ -140,14 +108,6 @@ QVIT_DEV void walk_row(const PruneMember& t, int64_t row, int lane, const Hyper&
       if (v) v[i] = vi;
     }
   }
-}
-
-// an item's group, checked against the tables; false: the item is skipped
-QVIT_DEV bool item_group(const PruneItem& it, const PruneGroup* groups, int ngroups, int nmembers, PruneGroup& G) {
-  if ((uint32_t)it.group >= (uint32_t)ngroups) return false;
-  G = groups[it.group];
-  return (uint32_t)it.row < (uint32_t)G.rows && G.member_begin >= 0 && G.member_count >= 0 &&
-         (int64_t)G.member_begin + G.member_count <= nmembers;
 }
 
 // ---- scores: per row sum p^2, sum g^2, sum p g over the members (importance_score/*.py) ---------------------------

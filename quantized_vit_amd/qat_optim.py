@@ -93,7 +93,9 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
     integer, kept on the device, and d_quant = d(that width) from then on.
 
     A parameter whose grad is None is skipped and its moments stay untouched. `grad_clip=(lo, hi)` clamps every
-    gradient as it is loaded (the reference's grad_clipping). After every step `invalidate()` is called on every
+    gradient as it is loaded (the reference's grad_clipping). `group_lasso_lambda` (with prune_groups) adds the training
+    drivers' group-lasso penalty over the prunable units to the gradients at the start of a step, before that clamp,
+    weighted per unit by gl_scale from the last period boundary. After every step `invalidate()` is called on every
     module of the model that has one: the kernels write through raw pointers, which does not move the version
     counter the packed-weight plans key on. All parameters must be contiguous float32 ROCm tensors (QvitError)."""
 
@@ -105,7 +107,8 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
                  max_bit_wt: int = 16, min_bit_act: int = 4, max_bit_act: int = 16,
                  grad_clip: Optional[Tuple[float, float]] = None, prune_groups: Optional[List[PruneGroup]] = None,
                  target_group_sparsity: float = 0.5, start_pruning_step: int = 1, pruning_steps: int = 1,
-                 pruning_periods: int = 1, group_divisible: int = 1, importance_score_criteria="default"):
+                 pruning_periods: int = 1, group_divisible: int = 1, importance_score_criteria="default",
+                 group_lasso_lambda: Optional[float] = None):
         if variant not in _VARIANTS:
             raise ValueError(f"variant = {variant!r}: expected one of {sorted(_VARIANTS)}")
         for name, lo, hi in (("wt", min_bit_wt, max_bit_wt), ("act", min_bit_act, max_bit_act)):
@@ -117,6 +120,10 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
         if prune_groups is not None:
             prune_groups = list(prune_groups)
             _check_prune_groups(prune_groups)
+        elif group_lasso_lambda is not None:
+            raise ValueError("group_lasso_lambda needs prune_groups: the penalty runs over their units")
+        self._lasso = group_lasso_lambda is not None
+        self.group_lasso_lambda = group_lasso_lambda
         self.model = model
         self.variant = variant
         self.start_projection_step = int(start_projection_step)
@@ -203,7 +210,7 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
         self._qtable = self._table(nq, _lib.QAT_QUANT_DTYPE)
         self._prune: Optional[_PruneState] = None if prune_groups is None else \
             _PruneState(self, prune_groups, float(target_group_sparsity), int(start_pruning_step), int(pruning_steps),
-                        int(pruning_periods), int(group_divisible), importance_score_criteria)
+                        int(pruning_periods), int(group_divisible), importance_score_criteria, lasso=self._lasso)
         # the chunk list (uploaded once), without the prune groups' members: qvit_prune_joint_apply steps those
         members = set() if self._prune is None else set(self._prune.member_dense)
         pairs = [(i, c) for i, (_, p) in enumerate(self._dense) if i not in members
@@ -211,6 +218,28 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
         self._nchunks = len(pairs)
         chunks = np.array(pairs or [(0, 0)], dtype=_lib.QAT_CHUNK_DTYPE)
         self._chunks = torch.from_numpy(chunks.view(np.int32).reshape(-1, 2)).to(self.device)
+
+    @property
+    def group_lasso_lambda(self) -> Optional[float]:
+        """The weight of the group-lasso penalty (the reference's --group_lasso_lambda); None: the optimizer was
+        built without it. May be reassigned between steps (0 during the reference's gl_start_epoch warm-up)."""
+        return self._lasso_lambda
+
+    @group_lasso_lambda.setter
+    def group_lasso_lambda(self, value: Optional[float]) -> None:
+        if (value is not None) != self._lasso:
+            raise ValueError("group_lasso_lambda is None or a number as the optimizer was built: construct it with "
+                             "group_lasso_lambda=0.0 to switch the penalty on later")
+        if value is not None and not (math.isfinite(value) and value >= 0.0):
+            raise ValueError(f"group_lasso_lambda = {value!r}: expected a finite number >= 0")
+        self._lasso_lambda = None if value is None else float(value)
+
+    def group_lasso_loss(self) -> torch.Tensor:
+        """The unweighted penalty sum_u scale_u ||unit u|| of the latest step that applied it (the reference's
+        gl_loss), a one-element device tensor; 0 before any such step. No host synchronisation."""
+        if not self._lasso:
+            raise ValueError("the optimizer was built without group_lasso_lambda")
+        return self._need_prune().lasso_loss
 
     def _table(self, rows: int, dtype: np.dtype) -> _Upload:
         """A device table of `rows` descriptors (_PruneState makes its own through this: qat_prune.py cannot import
@@ -310,6 +339,8 @@ class QuantAwareOptimizer(torch.optim.Optimizer):
                                count=len(self._dense))
             live = ptrs != 0
             if pr is not None:
+                if self._lasso_lambda:   # neither None nor 0: the penalty's gradient, before the clip and the scores
+                    pr.penalty(self._lasso_lambda, ptrs, live & ~self._seen)
                 pr.begin_step(n, ptrs, live & ~self._seen, hyper)   # the period boundary: scores and selection
             self._trow["grad"] = ptrs
             self._trow["flags"] = live & ~self._seen   # bit 0: the tensor's first step

@@ -23,7 +23,10 @@ if TYPE_CHECKING:
 #     back stay in the global list of taken rows, as in the reference, and are never selected again;
 #   * rows committed at a period's last step are written as zeros from the next step on (:1022 runs before :1026);
 #   * the joint branch steps the members without adamw's decay (:1008).
-# Left out: gl_scale (base_hybrid_sparse_optimizer.py:293-333) is computed by the reference and read by nothing.
+# gl_scale (base_hybrid_sparse_optimizer.py:293-333) is read by the training drivers' group-lasso penalty
+# (utils.py:181-189): with group_lasso_lambda set it is computed at every period boundary and the penalty weighs
+# every unit's norm by it (qvit_group_lasso_scale, qvit_group_lasso). A unit's norm there runs over all its members,
+# the weight row with its bias element, where the drivers take a norm per member tensor.
 # The one difference: `while d_quant < d_quant_lower` (:494) never ends for d_quant == 0; the device cuts it after 861
 # turns (x 1.25 per turn crosses fp32's exponent range) with d = d_quant_upper and gamma = 0.
 # Heads: the reference's multihead_numhead_transformation is view(num_groups, -1), which on a [3 dim, dim] qkv weight
@@ -223,16 +226,39 @@ def prune_tables(groups: List["_GroupState"], order: List[int], folded: bool, gr
             "units": np.concatenate(units) if units else empty, "joint": joint_groups}
 
 
+def lasso_tables(groups: List["_GroupState"], order: List[int]) -> dict:
+    """qvit_group_lasso's item tables, which do not change with the pruning state:
+      units  one entry per unit of every prunable group in `order` (the order of the scores): row = the unit, link =
+             the index in rows of its first row where it has several;
+      rows   the rows of those units, unit after unit in unit_rows_of's order, link = the unit's global index."""
+    units, rows = [], []
+    nrows = 0
+    for gi in order:
+        g = groups[gi]
+        if not g.prunable:
+            continue
+        per_unit = g.sections * g.unit_rows
+        ids = np.arange(g.num_groups)
+        units.append(_items(gi, ids, 0, 0 if g.basic else nrows + ids * per_unit))
+        if not g.basic:
+            rows.append(_items(gi, unit_rows_of(ids, g.num_groups, g.sections, g.unit_rows), 0,
+                               np.repeat(g.start + ids, per_unit)))
+            nrows += g.rows
+    empty = np.zeros(0, dtype=_lib.PRUNE_ITEM_DTYPE)
+    return {"units": np.concatenate(units) if units else empty, "rows": np.concatenate(rows) if rows else empty}
+
+
 class _PruneState:
     """The pruning half of QuantAwareOptimizer: the host bookkeeping of geta.py:904-919, :1024-1026 and the device
     tables of the qvit_prune_* entry points. The host's lists (important, active, pruned, the global ranking) count
     units; the device's items are physical rows, each with its unit's state. Per step: qvit_prune_joint_apply for the
     members of every group, and while any group has active redundant rows qvit_prune_joint_scalars, _reduce and
     _finish in front of it; at a period boundary qvit_prune_scores and its finish, followed by the step's one host
-    synchronisation."""
+    synchronisation. With `lasso`: the group-lasso penalty in front of a step (qvit_group_lasso) and gl_scale behind
+    every boundary's scores (qvit_group_lasso_scale)."""
 
     def __init__(self, opt: "QuantAwareOptimizer", groups: List[PruneGroup], sparsity: float, start: int, steps: int,
-                 periods: int, divisible: int, criteria):
+                 periods: int, divisible: int, criteria, lasso: bool = False):
         self.opt = opt
         self.groups = groups = [_GroupState(g) for g in groups]
         self.start, self.steps, self.divisible, self.sparsity = start, steps, divisible, sparsity
@@ -305,6 +331,21 @@ class _PruneState:
         self._jrow = np.zeros(2 * ng, dtype=_lib.QAT_QUANT_DTYPE)
         self._qsend = np.zeros_like(opt._qrow)
         self._member_group = np.repeat(np.arange(ng), [len(g.members) for g in groups])
+        self.lasso = bool(lasso)
+        if self.lasso:
+            t = lasso_tables(groups, self.order)
+            nu, self._lasso_nrows = self.total_num_groups, int(t["rows"].shape[0])
+            self._lasso_units = opt._table(nu, _lib.PRUNE_ITEM_DTYPE)
+            if nu:
+                self._lasso_units.send(t["units"])
+            self._lasso_rows = opt._table(self._lasso_nrows, _lib.PRUNE_ITEM_DTYPE) if self._lasso_nrows else None
+            if self._lasso_rows is not None:
+                self._lasso_rows.send(t["rows"])
+            self.gl_scale = torch.ones(max(nu, 1), dtype=torch.float32, device=dev)
+            self.has_gl_scale = False    # the reference's `"gl_scale" in group`: false until the first boundary
+            self._lasso_sumsq = torch.zeros(max(nu + self._lasso_nrows, 1), dtype=torch.float64, device=dev)
+            self._lasso_coef = torch.zeros(max(nu, 1), dtype=torch.float32, device=dev)
+            self.lasso_loss = torch.zeros(1, dtype=torch.float32, device=dev)
         self._tables()
 
     # ---- tables ---------------------------------------------------------------------------------------------------
@@ -340,9 +381,23 @@ class _PruneState:
                 g.active = []
                 g.important = [i for i in range(g.num_groups) if i not in g.pruned]
 
-    def begin_step(self, n: int, grad_ptrs: np.ndarray, fresh: np.ndarray, hyper: _lib.Hyper) -> None:
+    def _load_grads(self, grad_ptrs: np.ndarray, fresh: np.ndarray) -> None:
         self._mrow["grad"] = grad_ptrs[self.member_dense]
         self._mrow["flags"] = fresh[self.member_dense]   # bit 0: the tensor's first step
+
+    def penalty(self, lam: float, grad_ptrs: np.ndarray, fresh: np.ndarray) -> None:
+        """utils.py:157-194 and its backward(): lam * d/dp sum_u scale_u ||unit u|| into the members' gradients, the
+        unweighted sum into lasso_loss. In front of begin_step: a boundary's scores see the penalised gradient, and
+        the scale is the last boundary's (the reference forms its loss before its step())."""
+        self._load_grads(grad_ptrs, fresh)
+        self._send()
+        _lib.group_lasso(self._gtable.dev, len(self.groups), self._mtable.dev, self.nmembers, self._lasso_units.dev,
+                         self.total_num_groups, None if self._lasso_rows is None else self._lasso_rows.dev,
+                         self._lasso_nrows, self.gl_scale if self.has_gl_scale else None, lam, self._lasso_sumsq,
+                         self._lasso_coef, self.lasso_loss)
+
+    def begin_step(self, n: int, grad_ptrs: np.ndarray, fresh: np.ndarray, hyper: _lib.Hyper) -> None:
+        self._load_grads(grad_ptrs, fresh)
         if self._boundary(n):
             self._select(hyper)
         # before any launch of this step: the joint stage reads every member's gradient (compute_gamma_d would raise)
@@ -360,6 +415,10 @@ class _PruneState:
             if self.folded else {}
         _lib.prune_scores(self._gtable.dev, len(self.groups), self._mtable.dev, self.nmembers, self._itable.dev,
                           self.nprunable_rows, self._sums, self.weights, self._scores, hyper, **fold)
+        if self.lasso:   # base_hybrid_sparse_optimizer.py:293-333, on the scores as they lie on the device
+            _lib.group_lasso_scale(self._gtable.dev, len(self.groups), self._lasso_units.dev, self.total_num_groups,
+                                   self._scores, self.gl_scale)
+            self.has_gl_scale = True
         chosen = select_redundant(self._scores[:self.total_num_groups], self.taken, self.per_period[self.curr_period])
         self.taken.extend(chosen)
         for g in self.groups:
@@ -408,7 +467,8 @@ class _PruneState:
                 "active_redundant_idxes": [list(g.active) for g in self.groups],
                 "important_idxes": [list(g.important) for g in self.groups],
                 "pruned_group_idxes": list(self.taken), "curr_pruning_period": self.curr_period,
-                "target_num_redundant_groups": self.target}
+                "target_num_redundant_groups": self.target,
+                **({"gl_scale": self.gl_scale.detach().clone() if self.has_gl_scale else None} if self.lasso else {})}
 
     def load(self, st: dict) -> None:
         if st["group_names"] != [g.name for g in self.groups]:
@@ -419,6 +479,11 @@ class _PruneState:
         self.taken = list(st["pruned_group_idxes"])
         self.curr_period = int(st["curr_pruning_period"])
         self.target = int(st["target_num_redundant_groups"])
+        if self.lasso:   # a state saved without the penalty has no scale: as before the first boundary
+            scale = st.get("gl_scale")
+            self.has_gl_scale = scale is not None
+            if scale is not None:
+                self.gl_scale.copy_(scale)
         self._tables()
 
     @torch.no_grad()
