@@ -50,6 +50,8 @@
  *                             int8 x int4/int8 -> int32 MFMA contraction with a fused epilogue:
  *                             d_act * d_wt * acc + bias, optionally + residual (vit_model.py:206-207),
  *                             or GELU (vit_model.py:173) + the next layer's activation quantizer.
+ *   qvit_gemm_skinny          nothing of its own: a second schedule of qvit_gemm's contraction (quant_layers.py:
+ *                             495-499) for few rows (64 x 64 tiles, split-K reduced inside the launch), same bytes.
  *   qvit_gemm_wonly           quant_layers.py:495-499 in the default WEIGHT_ONLY mode (quant_model.py:23): fp32
  *                             activations x int4/int8 weight codes on bf16 MFMA (x split into three exact
  *                             bf16 terms), d_wt * acc + bias — F.linear(x, quantize_weight(W), b).
@@ -91,6 +93,7 @@
 #ifndef QVIT_HIP_H
 #define QVIT_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 #include <hip/hip_runtime_api.h>
 
@@ -698,6 +701,33 @@ int qvit_gemm_a32(const int8_t* A, int64_t M, int64_t K, const void* Wp, int wfm
                   const float* d_act, const float* d_wt, const float* bias, int epilogue, void* C, int64_t ldc,
                   int out_qtype, const float* out_d, const float* out_qm, const float* out_t, int out_levels,
                   const void* epi_table, hipStream_t stream);
+
+/*
+ * qvit_gemm_skinny: a second schedule of qvit_gemm's contraction (quant_layers.py:495-499) for few rows. It replaces
+ * nothing in the reference: same operands, same exact int32 accumulation, same epilogue arithmetic, so C is
+ * qvit_gemm's byte for byte on all five epilogues (QVIT_EPI_F32 .. QVIT_EPI_I32). One workgroup owns 64 rows x 64
+ * weight rows x one of `S` K-slices of whole 128-deep k-tiles; the slices of a tile meet in the workspace and the last
+ * to arrive reduces them and runs the epilogue, inside the one launch.
+ *   arguments up to epi_table : as qvit_gemm, checked in its order; then, with QVIT_EINVAL unless noted,
+ *   wfmt    : QVIT_W4R or QVIT_W8 only (callers run qvit_gemm for QVIT_W4 / QVIT_W8R);
+ *   M       : <= 4096, and ceil(M / 64) * npad / 64 <= 16384 tiles;
+ *   splits  : 0 -> S = clamp(2 CUs / tiles, 1, min(K / 128, 16)); > 0 forces S (> K / 128 or > 16 is rejected);
+ *   workspace : for S > 1, qvit_gemm_skinny_workspace bytes (NULL: QVIT_ENULL, fewer bytes: QVIT_EINVAL, not 16-byte
+ *             aligned: QVIT_EALIGN); not read for S == 1 (the query then gives 0 bytes). Its first 64 KiB are the
+ *             tiles' arrival counters, whatever the shape: they must be zero at the first use, and every completed
+ *             call leaves them zero, so one zero-initialised buffer serves calls of any shape with no clearing in
+ *             between. One workspace serves one stream at a time: calls that may run concurrently need a workspace
+ *             each.
+ * qvit_gemm_skinny_fits returns 1 for the shapes the call accepts (any splits aside), else 0.
+ * Special values: as qvit_gemm.
+ */
+int qvit_gemm_skinny_fits(int64_t M, int64_t K, int wfmt, int64_t N, int64_t npad, int epilogue);
+int qvit_gemm_skinny_workspace(int64_t M, int64_t K, int64_t npad, int splits, size_t* bytes);
+int qvit_gemm_skinny(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, int wfmt, int64_t N,
+                     int64_t npad, const float* d_act, const float* d_wt, const float* bias, int epilogue, void* C,
+                     int64_t ldc, int out_qtype, const float* out_d, const float* out_qm, const float* out_t,
+                     int out_levels, const void* epi_table, int splits, void* workspace, size_t workspace_bytes,
+                     hipStream_t stream);
 
 /*
  * Weight-only QuantizeLinear.forward (quant_layers.py:495-499, quant_mode WEIGHT_ONLY: quantize_act is the

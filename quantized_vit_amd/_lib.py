@@ -7,6 +7,7 @@ device pointers; every call is enqueued on torch's current HIP stream.
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 import threading
 from typing import NamedTuple, Optional, Tuple
@@ -171,6 +172,10 @@ _SIGNATURES = {
     "qvit_gemm_a32_fits": [_i64, _i32, _i64, _i64, _i32],
     "qvit_gemm_a32": [_c_p, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i32, _c_p, _c_p,
                       _c_p, _i32, _c_p, _c_p],
+    "qvit_gemm_skinny_fits": [_i64, _i64, _i32, _i64, _i64, _i32],
+    "qvit_gemm_skinny_workspace": [_i64, _i64, _i64, _i32, _c_p],
+    "qvit_gemm_skinny": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i32, _c_p, _i64,
+                         _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i32, _c_p, ctypes.c_size_t, _c_p],
     "qvit_gemm_wonly": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i64, _c_p, _i64, _c_p],
     "qvit_gemm_wgrad": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i64, _c_p, _i64, _c_p],
     "qvit_col2im_quant_backward": [_c_p, _i64, _c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
@@ -870,6 +875,54 @@ def gemm_a32(A: torch.Tensor, M: int, K: int, packed: torch.Tensor, wfmt: int, N
     _check(load().qvit_gemm_a32(_ptr(A), M, K, _ptr(packed), wfmt, N, npad, _ptr(d_act), _ptr(d_wt), _ptr(bias_pad),
                                 epilogue, _ptr(C), C.stride(0), out_qtype, _ptr(out_d), _ptr(out_qm), _ptr(out_t),
                                 out_levels, _ptr(epi_table), _stream(A.device)), "qvit_gemm_a32")
+    return C
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_skinny_fits(M: int, K: int, wfmt: int, N: int, npad: int, epilogue: int) -> bool:
+    """Whether qvit_gemm_skinny takes the shape (QVIT_W4R / QVIT_W8 images, 1 <= M <= 4096, the five epilogues).
+    Remembered per shape: gemm_codes asks at every call."""
+    return bool(load().qvit_gemm_skinny_fits(M, K, wfmt, N, npad, epilogue))
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_skinny_workspace_bytes(M: int, K: int, npad: int, splits: int = 0) -> int:
+    n = ctypes.c_size_t(0)
+    _check(load().qvit_gemm_skinny_workspace(M, K, npad, splits, ctypes.byref(n)), "qvit_gemm_skinny_workspace")
+    return int(n.value)
+
+
+_skinny_ws: dict = {}   # (device index, stream) -> zero-initialised workspace, grown on demand
+
+
+def gemm_skinny_workspace(device: torch.device, stream: int, nbytes: int) -> Optional[torch.Tensor]:
+    """The split-K workspace of qvit_gemm_skinny for launches on `stream` of `device`: one per (device, stream), as
+    a workspace serves one stream at a time. Its arrival counters start at zero and every call leaves them zero, so the
+    buffer is cleared only when it is made; a larger one replaces it when a call needs more."""
+    if nbytes == 0:
+        return None
+    key = (device.index, stream)
+    ws = _skinny_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        ws = _skinny_ws[key] = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
+def gemm_skinny(A: torch.Tensor, M: int, K: int, packed: torch.Tensor, wfmt: int, N: int, npad: int,
+                d_act: Optional[torch.Tensor], d_wt: Optional[torch.Tensor], bias_pad: Optional[torch.Tensor],
+                epilogue: int, C: torch.Tensor, out_qtype: int = 0, out_d=None, out_qm=None, out_t=None,
+                out_levels: int = 0, epi_table: Optional[torch.Tensor] = None, splits: int = 0,
+                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qvit_gemm_skinny: gemm's results byte for byte on the small-M split-K schedule (splits 0: the automatic
+    split). `workspace` defaults to the cached one of the current stream."""
+    _require_gpu(A, "codes")
+    stream = _stream(A.device)
+    if workspace is None:
+        workspace = gemm_skinny_workspace(A.device, stream, gemm_skinny_workspace_bytes(M, K, npad, splits))
+    _check(load().qvit_gemm_skinny(_ptr(A), M, K, A.stride(0), _ptr(packed), wfmt, N, npad, _ptr(d_act), _ptr(d_wt),
+                                   _ptr(bias_pad), epilogue, _ptr(C), C.stride(0), out_qtype, _ptr(out_d),
+                                   _ptr(out_qm), _ptr(out_t), out_levels, _ptr(epi_table), splits, _ptr(workspace),
+                                   0 if workspace is None else workspace.numel(), stream), "qvit_gemm_skinny")
     return C
 
 

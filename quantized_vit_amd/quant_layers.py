@@ -243,6 +243,14 @@ if GEMM_WREG not in ("w4", "w4r", "w8r"):
     raise ValueError(f"QVIT_GEMM_WREG={GEMM_WREG!r}: expected w4, w4r or w8r")
 GEMM_W4R = GEMM_WREG != "w4"   # a register image is in use
 
+# The int path's GEMMs at few rows (single-image and small-batch inference, the class-token tail of the last block):
+# with QVIT_GEMM_SKINNY=1, gemm_codes runs qvit_gemm_skinny (64 x 64 tiles, K split over workgroups and reduced inside
+# the launch; the same bytes as qvit_gemm) for M <= GEMM_SKINNY_MAX_M rows on the QVIT_W4R / QVIT_W8 images, and
+# qvit_gemm otherwise. Off by default. GEMM_SKINNY_MAX_M is the largest measured M at which the skinny schedule won on
+# the proj, fc1 and fc2 shapes of ViT-B and ViT-L alike (profiles/gemm_skinny_bench.txt).
+GEMM_SKINNY = os.environ.get("QVIT_GEMM_SKINNY", "0") == "1"
+GEMM_SKINNY_MAX_M = 256
+
 # The backward GEMMs of QuantizeLinear (behind F.linear's backward): "hip" runs both on the project's kernels,
 # dgrad (grad_out @ quantize_weight(W)) as qvit_gemm_wonly on the transposed weight codes wherever the plan holds
 # packed codes, wgrad (grad_out^T @ quantize_act(x)) as qvit_gemm_wgrad on the int8 activation codes of the
@@ -881,8 +889,10 @@ class QuantizeMixin:
         elif out is None:
             out = torch.empty((M, _lib.round_up(plan.n, 4)), dtype=torch.float32, device=dev)
         wimg, wfmt = plan.gemm_weights()
-        _lib.gemm(codes, M, plan.kpad, wimg, wfmt, plan.n, plan.npad, plan.d_act, plan.d_wt,
-                  plan.bias_pad, epilogue, out, *out_q, epi_table=table)
+        skinny = (GEMM_SKINNY and M <= GEMM_SKINNY_MAX_M
+                  and _lib.gemm_skinny_fits(M, plan.kpad, wfmt, plan.n, plan.npad, epilogue))
+        (_lib.gemm_skinny if skinny else _lib.gemm)(codes, M, plan.kpad, wimg, wfmt, plan.n, plan.npad, plan.d_act,
+                                                    plan.d_wt, plan.bias_pad, epilogue, out, *out_q, epi_table=table)
         return out
 
     def a32_fits(self, plan: QuantPlan, epilogue: int) -> bool:
