@@ -58,6 +58,10 @@
  *   qvit_gemm_wgrad           the backward of quant_layers.py:499's F.linear w.r.t. the quantized weight on the
  *                             integer path: fp32 grad_out^T x int8 activation codes on bf16 MFMA (the same exact
  *                             three-term split); the input's gradient is qvit_gemm_wonly on transposed codes.
+ *   qvit_gemm_f32_nt / qvit_gemm_f32_tn
+ *                             quant_layers.py:495-499 and its backward where neither operand is a code image
+ *                             (train.py:247-250 builds the model at num_bits = 32): fp32 x fp32 on bf16 MFMA, both
+ *                             operands split into three exact bf16 terms, six products per element pair.
  *   qvit_col2im_quant_backward  the backward of quant_layers.py:575-587 (QuantizeConv2d.forward) w.r.t. its input behind
  *                             the im2col lowering: col2im of the patch-row gradient fused with quantize_act's backward.
  *   qvit_conv_wonly           quant_layers.py:575-587 (QuantizeConv2d.forward, WEIGHT_ONLY) and quant_ultra.py:85-89
@@ -781,6 +785,44 @@ int64_t qvit_gemm_wgrad_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int qvit_gemm_wgrad(const float* G, int64_t M, int64_t N, int64_t ldg, const int8_t* A, int64_t K, int64_t lda,
                     const float* d_act, float* dW, int64_t ldw, void* workspace, int64_t workspace_bytes,
                     hipStream_t stream);
+
+/*
+ * QuantizeLinear's three contractions with two general fp32 operands (quant_layers.py:495-499: F.linear on
+ * quantize_act(x) and quantize_weight(W), and what autograd runs behind it), for the plans that hold no code image
+ * of an operand: weight levels beyond QVIT_W24 (train.py:247-250: the reference's driver builds its model with
+ * num_bits = 32 and reduces from there), fake-quantized activations beyond int8, the weight-only mode's input.
+ *   qvit_gemm_f32_nt  C[m][n] = sum_k A[m][k] B[n][k] (+ bias[n]): the forward (A = x_q [M][K], B = w_q [N][K]) and
+ *                     dgrad (A = grad_out, B = w_q^T). quant_layers.py:495-499; train.py:247-250.
+ *   qvit_gemm_f32_tn  C[i][j] = sum_m A[m][i] B[m][j]: wgrad (A = grad_out [M][I], B = x_q [M][J], C in the layout
+ *                     of nn.Linear.weight.grad). quant_layers.py:495-499; train.py:247-250.
+ *   A, B   : fp32, row strides lda, ldb >= the row's extent and % 4 == 0, 16-byte aligned. Rows are read in whole
+ *            16-byte groups, so the last group of a row may reach up to 3 floats into the row's padding [extent, ld);
+ *            whatever the padding holds never reaches C.
+ *   bias   : device float[N] or NULL (NT only).
+ *   C      : fp32. NT: [M][ldc], ldc >= N, ldc % 4 == 0, 16-byte aligned. TN: [I][ldc], ldc >= J, any 4-byte aligned
+ *            pointer and any ldc. Columns [extent, ldc) are not written.
+ *   workspace (TN) : qvit_gemm_f32_tn_workspace_bytes(M, I, J) bytes, 16-byte aligned, contents irrelevant. The M
+ *            range is split over s = max(1, min(16, ceil(M / 32), ceil(512 / tiles))) workgroups per output tile
+ *            (tiles = ceil(I / 128) ceil(J / 128)); their fp32 partials are summed in ascending split order by a
+ *            second launch. The query returns s * 128 ceil(I / 128) * 128 ceil(J / 128) * 4. NT has no split.
+ * Sizes: the output's extents in [1, 2^24] (NT: M >= 0, M == 0 does nothing), tiles <= 2^24, the contraction
+ * K in [1, 2^30] (NT) or M in [0, 2^30] (TN: M == 0 writes zeros); else QVIT_EINVAL, also from the query. The kernels
+ * index rows and columns in 32 bits and element offsets in 64. Misaligned bases or strides: QVIT_EALIGN (callers pad
+ * a copy). No atomics: the same call gives the same bits.
+ * fp32-GEMM accuracy: a = a1 + a2 + a3 and b = b1 + b2 + b3 exactly (bf16 terms by truncation), every product of two
+ * terms is exact in fp32, and a1b1, a1b2, a2b1, a2b2, a1b3, a3b1 are summed into one fp32 accumulator on
+ * v_mfma_f32_16x16x32_bf16, smallest first within each 32-deep stage. The dropped products are below
+ * (2^-21 + 2^-30) |a||b| per element pair; the result lies within (4 L + 9) 2^-24 (|A||B|) of the exact product for
+ * contraction length L.
+ * Special values: a NaN or Inf element of A or B makes every output that contracts it non-finite, and NaN where a
+ * library GEMM may give Inf (x - trunc(x) of Inf is NaN). NT: A[m][k] poisons row m of C, B[n][k] column n. TN:
+ * A[m][i] poisons row i, B[m][j] column j. No other output changes a bit.
+ */
+int qvit_gemm_f32_nt(const float* A, int64_t M, int64_t K, int64_t lda, const float* B, int64_t N, int64_t ldb,
+                     const float* bias, float* C, int64_t ldc, hipStream_t stream);
+int64_t qvit_gemm_f32_tn_workspace_bytes(int64_t M, int64_t I, int64_t J);
+int qvit_gemm_f32_tn(const float* A, int64_t M, int64_t I, int64_t lda, const float* B, int64_t J, int64_t ldb,
+                     float* C, int64_t ldc, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
 /*
  * The backward GEMMs of QuantizeConv2d on the integer path are those of QuantizeLinear over the patch rows the

@@ -124,6 +124,21 @@ def backward_ops(value, what: str) -> tuple:
         raise ValueError(f"{what}{sep}{value!r}: expected hip, torch, dgrad or wgrad") from None
 
 
+# Which of QuantizeLinear's three contractions run on qvit_gemm_f32_nt / _tn where the plan holds no code image of an
+# operand, by the value of quant_layers.F32_GEMM.
+F32_GEMM_OPS = {"torch": (), "hip": ("fwd", "dgrad", "wgrad"), "fwd": ("fwd",), "dgrad": ("dgrad",),
+                "wgrad": ("wgrad",)}
+
+
+def f32_gemm_ops(value, what: str) -> tuple:
+    """F32_GEMM_OPS[value]; `what` as in backward_ops."""
+    try:
+        return F32_GEMM_OPS[value]
+    except KeyError:
+        sep = "=" if what.startswith("QVIT_") else " = "
+        raise ValueError(f"{what}{sep}{value!r}: expected torch, hip, fwd, dgrad or wgrad") from None
+
+
 _c_p =ctypes.c_void_p
 _i64 = ctypes.c_int64
 _i32 = ctypes.c_int
@@ -178,6 +193,8 @@ _SIGNATURES = {
                          _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i32, _c_p, ctypes.c_size_t, _c_p],
     "qvit_gemm_wonly": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i64, _c_p, _i64, _c_p],
     "qvit_gemm_wgrad": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i64, _c_p, _i64, _c_p],
+    "qvit_gemm_f32_nt": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i64, _c_p],
+    "qvit_gemm_f32_tn": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _i64, _c_p, _i64, _c_p],
     "qvit_col2im_quant_backward": [_c_p, _i64, _c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                    _i32, _i32, _c_p, _c_p, _c_p, _f32, _f32, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_conv_wonly": [_c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_p, _i32,
@@ -233,6 +250,7 @@ INT64_FUNCS = {
     "qvit_gelu_quant_backward_workspace_bytes": [_i64],
     "qvit_attention_backward_workspace_bytes": [_i64, _i64, _i64],
     "qvit_gemm_wgrad_workspace_bytes": [_i64, _i64, _i64],
+    "qvit_gemm_f32_tn_workspace_bytes": [_i64, _i64, _i64],
     "qvit_col2im_quant_backward_workspace_bytes": [_i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                                    _i32],
     "qvit_ultra_weight_quant_backward_workspace_bytes": [_i64],
@@ -1018,6 +1036,86 @@ def gemm_wgrad(G: torch.Tensor, codes: torch.Tensor, K: int, d_act: torch.Tensor
     _check(lib.qvit_gemm_wgrad(_ptr(G), M, N, G.stride(0), _ptr(codes), K, codes.stride(0), _ptr(d_act), _ptr(out),
                                out.stride(0), _ptr(workspace), workspace.numel() * workspace.element_size(),
                                _stream(G.device)), "qvit_gemm_wgrad")
+    return out
+
+
+def _f32_gemm_operand(t: torch.Tensor, name: str) -> torch.Tensor:
+    """`t` as qvit_gemm_f32_nt / _tn read it: itself on the fast path (fp32, unit column stride, row stride a
+    multiple of 4 and at least the extent, 16-byte base, and the last row's last 16-byte group inside the storage:
+    rows are read in whole groups), else a copy with rows padded to a multiple of 4 (the padding zero)."""
+    _require_gpu(t, name)
+    assert t.dim() == 2, name
+    rows, cols = t.shape
+    ld = t.stride(0)
+    ok = t.dtype == torch.float32 and t.stride(1) == 1 and ld % 4 == 0 and ld >= cols and t.data_ptr() % 16 == 0
+    if ok and cols % 4:
+        end = t.storage_offset() + (rows - 1) * ld + round_up(cols, 4)
+        ok = end * 4 <= t.untyped_storage().nbytes()
+    if ok:
+        return t
+    p = torch.zeros((rows, round_up(cols, 4)), dtype=torch.float32, device=t.device)
+    p[:, :cols] = t
+    return p[:, :cols]
+
+
+def gemm_f32_nt(a: torch.Tensor, b: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a @ b^T (+ bias) on qvit_gemm_f32_nt: a [M, K], b [N, K], 2-d fp32 device tensors of any stride (an operand
+    off the kernel's alignment is copied into padded rows first), on torch's current stream. `out`: fp32 [M, N];
+    what lies behind its N columns stays untouched. Returns `out`, or a new [M, N] tensor (a view of rows padded to
+    a multiple of 4 when N is none)."""
+    a, b = _f32_gemm_operand(a, "a"), _f32_gemm_operand(b, "b")
+    (M, K), N = a.shape, b.shape[0]
+    assert b.shape[1] == K and K >= 1 and N >= 1
+    if bias is not None:
+        _require_gpu(bias, "bias")
+        bias = bias.detach().float().contiguous()
+        assert bias.shape == (N,)
+    y = out
+    if y is None or y.dtype != torch.float32 or y.stride(1) != 1 or y.stride(0) % 4 or y.data_ptr() % 16:
+        y = torch.empty((M, round_up(N, 4)), dtype=torch.float32, device=a.device)[:, :N]
+    assert y.shape == (M, N) and y.is_cuda
+    if M > 0:   # (an empty tensor has no device pointer to hand over)
+        _check(load().qvit_gemm_f32_nt(_ptr(a), M, K, a.stride(0), _ptr(b), N, b.stride(0), _ptr(bias), _ptr(y),
+                                       y.stride(0), _stream(a.device)), "qvit_gemm_f32_nt")
+    if out is not None and y is not out:
+        out.copy_(y)
+        return out
+    return y
+
+
+def gemm_f32_tn_splits(M: int, I: int, J: int) -> int:
+    """Workgroups per output tile over which qvit_gemm_f32_tn splits the M range (from its workspace query)."""
+    nbytes = int(load().qvit_gemm_f32_tn_workspace_bytes(M, I, J))
+    if nbytes < 0:
+        raise QvitError(f"qvit_gemm_f32_tn_workspace_bytes({M}, {I}, {J}) failed (status {nbytes})")
+    return nbytes // (round_up(I, 128) * round_up(J, 128) * 4)
+
+
+def gemm_f32_tn(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None,
+                workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a^T @ b on qvit_gemm_f32_tn: a [M, I], b [M, J], 2-d fp32 device tensors of any stride (copied into padded
+    rows where the kernel's alignment demands it), on torch's current stream. `out`: fp32 [I, J] rows of any stride
+    (what lies behind the J columns stays untouched); `workspace`: float32, at least the query's bytes, contents
+    irrelevant. M == 0 writes zeros."""
+    a, b = _f32_gemm_operand(a, "a"), _f32_gemm_operand(b, "b")
+    (M, I), J = a.shape, b.shape[1]
+    assert b.shape[0] == M and I >= 1 and J >= 1
+    if out is None:
+        out = torch.empty((I, J), dtype=torch.float32, device=a.device)
+    assert out.dtype == torch.float32 and out.shape == (I, J) and out.stride(1) == 1 and out.is_cuda
+    if M == 0:
+        out.zero_()
+        return out
+    lib = load()
+    nbytes = int(lib.qvit_gemm_f32_tn_workspace_bytes(M, I, J))
+    if nbytes < 0:
+        _check(nbytes, "qvit_gemm_f32_tn_workspace_bytes")
+    if workspace is None:
+        workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=a.device)
+    _check(lib.qvit_gemm_f32_tn(_ptr(a), M, I, a.stride(0), _ptr(b), J, b.stride(0), _ptr(out), out.stride(0),
+                                _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(a.device)),
+           "qvit_gemm_f32_tn")
     return out
 
 

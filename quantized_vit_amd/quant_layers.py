@@ -264,6 +264,21 @@ def _backward_gemm_ops() -> tuple:
     return _lib.backward_ops(BACKWARD_GEMM, "BACKWARD_GEMM")
 
 
+# QuantizeLinear's contractions of two general fp32 operands, where the plan holds no code image to contract: the
+# forward of a plan beyond every packed format (weight levels above 65536: the 32..17-bit stages of a QAT run that
+# starts at num_bits = 32), its dgrad, and wgrad wherever the layer is off the integer path (those stages, W+A layers
+# whose activations are fake-quantized to fp32, the whole weight-only mode). "torch" (the default) keeps them on the
+# library's fp32 GEMMs (F.linear / torch.mm); "hip" runs all three on qvit_gemm_f32_nt / qvit_gemm_f32_tn (both
+# operands split into three bf16 terms, six MFMA products); "fwd" / "dgrad" / "wgrad" select one op. A backward op
+# runs there only if BACKWARD_GEMM admits it too. QVIT_F32_GEMM sets it (measurement: DESIGN.md section 32).
+F32_GEMM = os.environ.get("QVIT_F32_GEMM", "torch")
+_lib.f32_gemm_ops(F32_GEMM, "QVIT_F32_GEMM")   # an unknown value stops the import
+
+
+def _f32_gemm_ops() -> tuple:
+    return _lib.f32_gemm_ops(F32_GEMM, "F32_GEMM")
+
+
 # The backward GEMMs of QuantizeConv2d (behind F.conv2d's backward), a switch of its own: "hip" runs both on the
 # project's kernels wherever the layer is eligible (groups 1, zero padding, packed codes), wgrad as qvit_gemm_wgrad
 # on the recomputed im2col codes (integer path), dgrad as qvit_gemm_wonly on the transposed weight codes followed by
@@ -809,7 +824,7 @@ class QuantizeMixin:
         # (an op on its HIP route reads the integer codes instead: BACKWARD_GEMM)
         w_q = self.w_fakequant(plan).view_as(weight) if need_xq and not hip_x else None
         x_q = None
-        if need_wq and not hip_w:
+        if need_wq and hip_w is not True:   # torch.mm's and qvit_gemm_f32_tn's fp32 operand
             x_q = _lib.fake_quant_f32(xf, *plan.act_q) if wa else xf
         act_done = ()   # QuantizeConv2d's dgrad: the activation quantizer's backward ran with it, (its scalars,)
         if hip_x or hip_w:
@@ -1054,16 +1069,34 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
     def _backward_gemm_routes(self, plan, need_xq, need_wq):
         ops = _backward_gemm_ops()
         has_codes = plan.int_path or bool(plan.extra.get("wonly"))
-        return (need_xq and "dgrad" in ops and has_codes,
-                need_wq and "wgrad" in ops and plan.int_path)
+        f32 = tuple(op for op in _f32_gemm_ops() if op in ops)
+        # a route: False (torch.mm), True (the code kernels) or "f32" (qvit_gemm_f32_*: no code image to contract)
+        hip_x = need_xq and "dgrad" in ops and has_codes
+        hip_w = need_wq and "wgrad" in ops and plan.int_path
+        if need_xq and not has_codes and "dgrad" in f32:
+            hip_x = "f32"
+        if need_wq and not plan.int_path and "wgrad" in f32:
+            hip_w = "f32"
+        return hip_x, hip_w
+
+    def _w_fakequant_t(self, plan) -> torch.Tensor:
+        """quantize_weight(W)^T, contiguous [k, n] fp32: dgrad's second operand on qvit_gemm_f32_nt. Cached in the
+        plan's extra, so it lives and dies with the plan (a training-mode plan is rebuilt on every step)."""
+        if "w_fakequant_t" not in plan.extra:
+            plan.extra["w_fakequant_t"] = self.w_fakequant(plan).reshape(plan.n, plan.k).t().contiguous()
+        return plan.extra["w_fakequant_t"]
 
     def _gemm_grads_hip(self, plan, xf, x_q, w_q, G, hip_x, hip_w):
+        # (_backward_plan forms x_q / w_q exactly for the routes that read them: torch.mm's and the f32 wgrad's)
         G2 = G.reshape(-1, plan.n)
-        M = G2.shape[0]
         grad_xq, grad_wq = self._gemm_grads(plan, tuple(xf.shape), None if hip_w else x_q, None if hip_x else w_q, G)
-        if hip_x:
+        if hip_x == "f32":
+            grad_xq = _lib.gemm_f32_nt(G2, self._w_fakequant_t(plan)).contiguous()
+        elif hip_x:
             grad_xq = self._dgrad_hip(plan, G2)
-        if hip_w:
+        if hip_w == "f32":
+            grad_wq = _lib.gemm_f32_tn(G2, x_q.reshape(-1, plan.k))
+        elif hip_w:
             # G^T @ (d_act codes): the int8 codes the forward contracted (the same quant_code)
             x2 = xf.reshape(-1, plan.k)
             grad_wq = _lib.gemm_wgrad(G2, self._act_codes(x2, plan), plan.k, plan.d_act)
@@ -1124,7 +1157,11 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
             return y.reshape(*input_.shape[:-1], plan.n)
         x = self.quantize_act(input_.float()) if self.quant_mode == QuantizationMode.WEIGHT_AND_ACTIVATION \
             else input_.float()
-        return F.linear(x.detach(), self.w_fakequant(plan), None if self.bias is None else self.bias.detach())
+        bias = None if self.bias is None else self.bias.detach()
+        if "fwd" in _f32_gemm_ops():
+            y = _lib.gemm_f32_nt(x.detach().reshape(-1, plan.k), self.w_fakequant(plan).reshape(plan.n, plan.k), bias)
+            return y.reshape(*input_.shape[:-1], plan.n)
+        return F.linear(x.detach(), self.w_fakequant(plan), bias)
 
 
 # ---- train-time fusion: LayerNorm / GELU feeding a QuantizeLinear as one autograd node -------------------------
