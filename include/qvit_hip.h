@@ -62,6 +62,9 @@
  *                             quant_layers.py:495-499 and its backward where neither operand is a code image
  *                             (train.py:247-250 builds the model at num_bits = 32): fp32 x fp32 on bf16 MFMA, both
  *                             operands split into three exact bf16 terms, six products per element pair.
+ *   qvit_quantize_act_i16 / qvit_gemm_a16 / qvit_weight_code_sums
+ *                             quant_layers.py:495-499 with 9- to 16-bit activation codes: the codes as two int8 digit
+ *                             planes, contracted with the weight digits on int8 MFMA, exact.
  *   qvit_col2im_quant_backward  the backward of quant_layers.py:575-587 (QuantizeConv2d.forward) w.r.t. its input behind
  *                             the im2col lowering: col2im of the patch-row gradient fused with quantize_act's backward.
  *   qvit_conv_wonly           quant_layers.py:575-587 (QuantizeConv2d.forward, WEIGHT_ONLY) and quant_ultra.py:85-89
@@ -125,7 +128,7 @@ extern "C" {
                        (qvit_pack_weight_w4r); same results, each wave's weight rows loaded into registers */
 #define QVIT_W8R 80 /* qvit_gemm / qvit_gemm_qkv_split only: QVIT_W4 codes in the int8 register image
                        (qvit_pack_weight_w8r); same results, no unpack in the main loop, twice the bytes  */
-#define QVIT_W16 16 /* qvit_gemm_wonly only: codes |k| <= 32639 as balanced base-256 digits k = 256 h + l, h and l
+#define QVIT_W16 16 /* qvit_gemm_wonly / qvit_gemm_a16 only: codes |k| <= 32639 as balanced base-256 digits k = 256 h + l, h and l
                        in [-128, 127], two QVIT_W8 images of npad * kpad bytes (h, then l; qvit_pack_weight)  */
 #define QVIT_W24 24 /* the same with three digits k = 65536 a + 256 h + l (|k| < 2^23, e.g. 16-bit layers whose
                        saturation code is 32768): three QVIT_W8 images, a, h, l                               */
@@ -823,6 +826,49 @@ int qvit_gemm_f32_nt(const float* A, int64_t M, int64_t K, int64_t lda, const fl
 int64_t qvit_gemm_f32_tn_workspace_bytes(int64_t M, int64_t I, int64_t J);
 int qvit_gemm_f32_tn(const float* A, int64_t M, int64_t I, int64_t lda, const float* B, int64_t J, int64_t ldb,
                      float* C, int64_t ldc, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/*
+ * QuantizeLinear.forward (quant_layers.py:495-499) in WEIGHT_AND_ACTIVATION mode with activation levels 128 .. 32767
+ * (9 to 16 bits: the default model_to_quantize_model(num_bits = 16), and a QAT run on its way down), as an exact
+ * integer contraction on int8 MFMA: Y[m][n] = d_act d_wt sum_k k_a[m][k] k_w[n][k] + bias[n].
+ *
+ * qvit_quantize_act_i16: qvit_quantize_act_i8's arguments, checks (in its order) and quantizer (quant_code), with the
+ * code k clamped to [-32768, 32767] and written as two int8 digits, k = 256 hi + lo + 128 with hi = k >> 8
+ * (arithmetic shift) and lo = (k & 255) - 128, both in [-128, 127].
+ *   planes : int8 [2][rows][ldc], the hi plane first (the lo plane starts rows * ldc bytes on); kpad <= ldc,
+ *            kpad % 16 == 0, ldc % 16 == 0, 16-byte aligned. Columns [cols, kpad) hold the code 0: hi = 0, lo = -128.
+ *   Special values as qvit_quantize_act_i8: a NaN gives the code 0, +-Inf and +-FLT_MAX +-min(L, 32767).
+ *
+ * qvit_weight_code_sums: sums[n] = sum_k k_w[n][k] (int64, n < npad) of a packed weight image, the per-column term
+ * the activation digits' offset of 128 costs; run once per image. For QVIT_W4 the sums are those of the bytes 16 k_w
+ * the GEMM contracts. Checks: Wp / sums NULL (QVIT_ENULL); wfmt, npad, K as qvit_gemm_a16 (QVIT_EINVAL); Wp 16-byte,
+ * sums 8-byte aligned (QVIT_EALIGN).
+ *
+ * qvit_gemm_a16:
+ *   A      : the digit planes, int8 [2][M][lda] (the lo plane M * lda bytes after the hi plane), K valid columns.
+ *   Wp     : the packed image as qvit_gemm_wonly takes it: QVIT_W4 / QVIT_W8 from qvit_pack_weight (QVIT_W4 is
+ *            unpacked in the kernel), QVIT_W16 / QVIT_W24 the QVIT_W8 digit images back to back.
+ *   d_act, d_wt : device float[1]; bias : device float[npad] (padded) or NULL; wsum : qvit_weight_code_sums of Wp.
+ *   Y      : fp32 [M][ldy]; outputs for n >= N are not written.
+ * Checks, in this order: A, Wp, Y, d_act, d_wt or wsum NULL: QVIT_ENULL. Then QVIT_EINVAL: wfmt none of the four;
+ * M < 0 or M > 2^24; K <= 0, K % QVIT_TILE_K or K > 32768; N <= 0, npad < N, npad % QVIT_TILE_N or npad > 2^24; more
+ * than 2^30 tiles; lda < K; ldy < N. Then QVIT_EALIGN: lda % 16, ldy % 4, A / Wp / Y / bias not 16-byte or wsum not
+ * 8-byte aligned. M == 0 does nothing. qvit_gemm_a16_fits returns 1 exactly when the size checks (everything before
+ * lda) pass.
+ * K <= 32768: the products accumulate in one int32 set per power of 256 (weight digits + 1 sets, at most two
+ * products of magnitude <= 2^14 per k and set), exact up to that K. The sets are combined in int64, and
+ * y = fp32(fp64(d_act d_wt) * S + bias) with the sum in fp64: |y - y_exact| <= 2^-24 |y| + 2^-52 (|d_act d_wt S| +
+ * |bias|), one fp32 rounding of a value exact to fp64. No atomics, no workspace: the same call gives the same bits.
+ * Small M launches fewer tiles (256 weight rows x 64 rows, 32 for QVIT_W24); there is no split-K.
+ */
+int qvit_quantize_act_i16(const float* x, int64_t rows, int64_t cols, int64_t ldx, int qtype, const float* d_quant,
+                          const float* q_m, const float* t_quant, int levels, int8_t* planes, int64_t ldc,
+                          int64_t kpad, hipStream_t stream);
+int qvit_weight_code_sums(const void* Wp, int wfmt, int64_t npad, int64_t K, int64_t* sums, hipStream_t stream);
+int qvit_gemm_a16_fits(int64_t M, int64_t K, int wfmt, int64_t N, int64_t npad);
+int qvit_gemm_a16(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, int wfmt, int64_t N,
+                  int64_t npad, const float* d_act, const float* d_wt, const float* bias, const int64_t* wsum,
+                  float* Y, int64_t ldy, hipStream_t stream);
 
 /*
  * The backward GEMMs of QuantizeConv2d on the integer path are those of QuantizeLinear over the patch rows the

@@ -29,7 +29,7 @@ W4 = 4
 W8 = 8
 W4R = 40  # qvit_gemm / qvit_gemm_qkv_split only: a W4 image re-ordered by qvit_pack_weight_w4r
 W8R = 80  # qvit_gemm / qvit_gemm_qkv_split only: a W4 image as 16x-scaled int8 operands (qvit_pack_weight_w8r)
-W16 = 16  # qvit_gemm_wonly only: balanced base-256 digits as W8 images, two (|k| <= 32639) or
+W16 = 16  # qvit_gemm_wonly / qvit_gemm_a16 only: balanced base-256 digits as W8 images, two (|k| <= 32639) or
 W24 = 24  # three (|k| < 2^23)
 
 EPI_F32 = 0
@@ -193,6 +193,10 @@ _SIGNATURES = {
                          _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i32, _c_p, ctypes.c_size_t, _c_p],
     "qvit_gemm_wonly": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i64, _c_p, _i64, _c_p],
     "qvit_gemm_wgrad": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i64, _c_p, _i64, _c_p],
+    "qvit_quantize_act_i16": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i64, _c_p],
+    "qvit_weight_code_sums": [_c_p, _i32, _i64, _i64, _c_p, _c_p],
+    "qvit_gemm_a16_fits": [_i64, _i64, _i32, _i64, _i64],
+    "qvit_gemm_a16": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_gemm_f32_nt": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i64, _c_p],
     "qvit_gemm_f32_tn": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _i64, _c_p, _i64, _c_p],
     "qvit_col2im_quant_backward": [_c_p, _i64, _c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
@@ -991,6 +995,55 @@ def gemm_wonly_rows(x2: torch.Tensor, k: int, kpad: int, packed: torch.Tensor, w
     y = torch.empty((M, ldy), dtype=torch.float32, device=x2.device)
     gemm_wonly(x2, M, kpad, packed, wfmt, n, npad, d_wt, bias_pad, y)
     return y if ldy == n else y[:, :n]
+
+
+A16_MAX_K = 32768   # gemm_a16.hip A16_MAX_K: the int32 accumulator sets of qvit_gemm_a16 are exact up to this K
+
+
+def quantize_act_i16(x2d: torch.Tensor, qtype: int, d: Optional[torch.Tensor], qm: Optional[torch.Tensor],
+                     t: Optional[torch.Tensor], levels: int, out: torch.Tensor, kpad: int) -> torch.Tensor:
+    """quantize_act_i8 for codes up to 16 bits, as two int8 digit planes: out is int8 [2, rows, >= kpad] (contiguous),
+    hi = k >> 8 first, then lo = (k & 255) - 128 (k = 256 hi + lo + 128); the operand of gemm_a16."""
+    _require_gpu(x2d, "input")
+    assert x2d.dtype == torch.float32 and x2d.dim() == 2 and x2d.stride(1) == 1
+    rows, cols = x2d.shape
+    assert out.dtype == torch.int8 and out.is_contiguous() and tuple(out.shape[:2]) == (2, rows)
+    _check(load().qvit_quantize_act_i16(_ptr(x2d), rows, cols, x2d.stride(0), qtype, _ptr(d), _ptr(qm), _ptr(t),
+                                        levels, _ptr(out), out.stride(1), kpad, _stream(x2d.device)),
+           "qvit_quantize_act_i16")
+    return out
+
+
+def digits_to_codes(planes: torch.Tensor) -> torch.Tensor:
+    """The int32 codes [rows, ld] behind the digit planes of quantize_act_i16."""
+    return 256 * planes[0].to(torch.int32) + planes[1].to(torch.int32) + 128
+
+
+def weight_code_sums(packed: torch.Tensor, wfmt: int, npad: int, kpad: int) -> torch.Tensor:
+    """int64 [npad]: sum_k of every weight row's codes as gemm_a16 contracts them (qvit_weight_code_sums)."""
+    _require_gpu(packed, "packed weights")
+    sums = torch.empty(npad, dtype=torch.int64, device=packed.device)
+    _check(load().qvit_weight_code_sums(_ptr(packed), wfmt, npad, kpad, _ptr(sums), _stream(packed.device)),
+           "qvit_weight_code_sums")
+    return sums
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_a16_fits(M: int, K: int, wfmt: int, N: int, npad: int) -> bool:
+    """Whether qvit_gemm_a16 takes the shape (W4 / W8 / W16 / W24 images, K <= A16_MAX_K)."""
+    return bool(load().qvit_gemm_a16_fits(M, K, wfmt, N, npad))
+
+
+def gemm_a16(A: torch.Tensor, M: int, K: int, packed: torch.Tensor, wfmt: int, N: int, npad: int,
+             d_act: torch.Tensor, d_wt: torch.Tensor, bias_pad: Optional[torch.Tensor], wsum: torch.Tensor,
+             Y: torch.Tensor) -> torch.Tensor:
+    """Y = d_act d_wt (codes_a @ codes_w^T) + bias, exact integer contraction of the digit planes A (int8 [2, M, lda],
+    quantize_act_i16) with the packed weight digits (qvit_gemm_a16); wsum = weight_code_sums(packed, ...)."""
+    _require_gpu(A, "digit planes")
+    assert A.dtype == torch.int8 and A.is_contiguous() and tuple(A.shape[:2]) == (2, M)
+    _check(load().qvit_gemm_a16(_ptr(A), M, K, A.stride(1), _ptr(packed), wfmt, N, npad, _ptr(d_act), _ptr(d_wt),
+                                _ptr(bias_pad), _ptr(wsum), _ptr(Y), Y.stride(0), _stream(A.device)), "qvit_gemm_a16")
+    return Y
 
 
 def gemm_wgrad_splits(M: int, N: int, K: int) -> int:

@@ -279,6 +279,14 @@ def _f32_gemm_ops() -> tuple:
     return _lib.f32_gemm_ops(F32_GEMM, "F32_GEMM")
 
 
+# QuantizeLinear's forward in W+A mode with activation levels 128 .. 32767 (9 to 16 bits) on a plan that holds packed
+# weight codes: with QVIT_A16_GEMM=1 the activations are quantized to 16-bit codes as two int8 digit planes
+# (qvit_quantize_act_i16) and contracted exactly with the weight digits on int8 MFMA (qvit_gemm_a16), instead of
+# qvit_fake_quant_f32 followed by qvit_gemm_wonly. Off by default (measurement: DESIGN.md section 33); the backward is
+# the same on either route.
+A16_GEMM = os.environ.get("QVIT_A16_GEMM", "0") == "1"
+
+
 # The backward GEMMs of QuantizeConv2d (behind F.conv2d's backward), a switch of its own: "hip" runs both on the
 # project's kernels wherever the layer is eligible (groups 1, zero padding, packed codes), wgrad as qvit_gemm_wgrad
 # on the recomputed im2col codes (integer path), dgrad as qvit_gemm_wonly on the transposed weight codes followed by
@@ -1139,6 +1147,29 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
                 grad_w.view_as(weight).to(weight.dtype) if need_w else None,
                 grad_b) + self._scalar_grads(scalars, needs[5:11])
 
+    def _a16_route(self, plan: QuantPlan, M: int) -> bool:
+        """The forward of a plan with packed codes runs on qvit_quantize_act_i16 + qvit_gemm_a16 (A16_GEMM)."""
+        return (A16_GEMM and bool(plan.extra.get("wonly"))
+                and self.quant_mode == QuantizationMode.WEIGHT_AND_ACTIVATION
+                and 128 <= abs(plan.level_act) <= 32767
+                and _lib.gemm_a16_fits(M, plan.kpad, plan.wfmt, plan.n, plan.npad))
+
+    def _a16_rows(self, x2: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
+        """[M, k] rows -> quantize_act(x2) @ quantize_weight(W)^T + b as [M, n], the contraction on the integer codes
+        of both operands. The per-column code sums of the weight image are made once per plan."""
+        if x2.dtype != torch.float32 or x2.stride(-1) != 1:
+            x2 = x2.float().contiguous()
+        M = x2.shape[0]
+        if "a16_wsum" not in plan.extra:
+            plan.extra["a16_wsum"] = _lib.weight_code_sums(plan.packed, plan.wfmt, plan.npad, plan.kpad)
+        planes = torch.empty((2, M, plan.kpad), dtype=torch.int8, device=x2.device)
+        _lib.quantize_act_i16(x2, *plan.act_q, 0, planes, plan.kpad)
+        ldy = _lib.round_up(plan.n, 4)
+        y = torch.empty((M, ldy), dtype=torch.float32, device=x2.device)
+        _lib.gemm_a16(planes, M, plan.kpad, plan.packed, plan.wfmt, plan.n, plan.npad, plan.d_act, plan.d_wt,
+                      plan.bias_pad, plan.extra["a16_wsum"], y)
+        return y if ldy == plan.n else y[:, :plan.n]
+
     def _forward_plan(self, input_: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
         if plan.int_path:
             x2 = input_.detach().reshape(-1, plan.k)
@@ -1151,6 +1182,8 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
                 out = out[:, :plan.n].contiguous()
             return out.view(*input_.shape[:-1], plan.n)
         if plan.extra.get("wonly"):
+            if self._a16_route(plan, input_.numel() // plan.k):
+                return self._a16_rows(input_.detach().reshape(-1, plan.k), plan).reshape(*input_.shape[:-1], plan.n)
             x = self.quantize_act(input_.float()) if self.quant_mode == QuantizationMode.WEIGHT_AND_ACTIVATION \
                 else input_
             y = self._wonly_rows(x.detach().reshape(-1, plan.k), plan)
