@@ -65,6 +65,10 @@
  *   qvit_quantize_act_i16 / qvit_gemm_a16 / qvit_weight_code_sums
  *                             quant_layers.py:495-499 with 9- to 16-bit activation codes: the codes as two int8 digit
  *                             planes, contracted with the weight digits on int8 MFMA, exact.
+ *   qvit_quantize_act_i4 / qvit_gemm_a4
+ *                             quant_layers.py:356-381 and :495-499 with at most 7 activation levels (num_bits = 4 on
+ *                             both operands): the codes as packed nibbles (QVIT_ACT_P4), qvit_gemm's contraction and
+ *                             epilogues on them, same bytes.
  *   qvit_col2im_quant_backward  the backward of quant_layers.py:575-587 (QuantizeConv2d.forward) w.r.t. its input behind
  *                             the im2col lowering: col2im of the patch-row gradient fused with quantize_act's backward.
  *   qvit_conv_wonly           quant_layers.py:575-587 (QuantizeConv2d.forward, WEIGHT_ONLY) and quant_ultra.py:85-89
@@ -869,6 +873,48 @@ int qvit_gemm_a16_fits(int64_t M, int64_t K, int wfmt, int64_t N, int64_t npad);
 int qvit_gemm_a16(const int8_t* A, int64_t M, int64_t K, int64_t lda, const void* Wp, int wfmt, int64_t N,
                   int64_t npad, const float* d_act, const float* d_wt, const float* bias, const int64_t* wsum,
                   float* Y, int64_t ldy, hipStream_t stream);
+
+/*
+ * QVIT_ACT_P4: activation codes of at most 4 bits as packed nibbles, the input of qvit_gemm_a4
+ * (QuantizeLinear.forward, quant_layers.py:495-499, with at most 7 activation levels: num_bits = 4 on both operands).
+ * An [M][kpad] code matrix (kpad % 128 == 0, codes in [-7, 7]) is stored as [M][ldp] bytes, ldp >= kpad / 2,
+ * ldp % 16 == 0, 16-byte aligned. Inside each 128-column k-tile t, byte j (0..63) of the row's 64-byte group (at byte
+ * 64 t of the row) holds column 128 t + j in its low nibble and column 128 t + 64 + j in its high nibble, both two's
+ * complement. One 16-byte fragment read therefore yields a GEMM lane's int8 MFMA operand for both 64-deep k-steps of
+ * the tile, as the bytes 16 a: (p << 4) & 0xF0F0F0F0 is the first step, p & 0xF0F0F0F0 the second. Padding columns
+ * [K, kpad) hold the code 0; bytes [kpad / 2, ldp) are never touched.
+ *
+ * qvit_quantize_act_i4: qvit_quantize_act_i8's arguments, checks (in its order; kpad % 128 == 0, ldp >= kpad / 2,
+ * else QVIT_EINVAL; ldp % 16 or packed off 16 bytes: QVIT_EALIGN) and quantizer (quant_code, guarded and careful
+ * paths), with the codes saturated at +-7 and written in QVIT_ACT_P4. Unpacked, the output is
+ * qvit_quantize_act_i8's byte for byte whenever the saturation code L is at most 7; the caller keeps layers above 7
+ * off this route, as it keeps layers above 127 off int8.
+ *   Special values as qvit_quantize_act_i8: a NaN gives the code 0, +-Inf and +-FLT_MAX +-min(L, 7).
+ *
+ * qvit_gemm_a4: qvit_gemm's contraction and its five epilogues (QVIT_EPI_F32 .. QVIT_EPI_I32, same arithmetic, same
+ * code table) with A in QVIT_ACT_P4; C is qvit_gemm's on the unpacked codes, byte for byte.
+ *   A, ldp : the packed codes, K = kpad valid columns (ldp >= K / 2).
+ *   wfmt   : QVIT_W4R or QVIT_W8 only (the two images qvit_gemm_skinny takes).
+ *   every other argument as qvit_gemm (C of the int8 epilogues: ldc % 4 == 0, 4-byte aligned, as qvit_gemm_skinny).
+ * Both operands are unpacked in registers to the bytes 16 x, so the int32 accumulators hold 256 acc (QVIT_W4R) or
+ * 16 acc (QVIT_W8); the power of two is folded into alpha, or shifted away for QVIT_EPI_I32. |16 w 16 a| <= 128 * 112,
+ * so K <= 65536 keeps |sum| <= 9.4e8 < 2^31 for both formats; a larger K is QVIT_EINVAL.
+ * Checks, in this order: A, Wp or C NULL: QVIT_ENULL. Then QVIT_EINVAL: wfmt neither of the two; M < 0 or
+ * M > INT32_MAX / 2; K <= 0, K % QVIT_TILE_K or K > 65536; N <= 0, npad < N, npad % QVIT_TILE_N or
+ * npad > INT32_MAX / 2; more than 2^30 tiles; ldp < K / 2. Then ldp % 16 or A / Wp off 16 bytes: QVIT_EALIGN; from
+ * the epilogue on as qvit_gemm_skinny. M == 0 does nothing. qvit_gemm_a4_fits returns 1 exactly when the size checks
+ * (everything before ldp) and the epilogue's range pass.
+ * One workgroup per 256 weight rows x 128 rows; no atomics, no workspace: the same call gives the same bits.
+ * Special values: as qvit_gemm.
+ */
+int qvit_quantize_act_i4(const float* x, int64_t rows, int64_t cols, int64_t ldx, int qtype, const float* d_quant,
+                         const float* q_m, const float* t_quant, int levels, uint8_t* packed, int64_t ldp,
+                         int64_t kpad, hipStream_t stream);
+int qvit_gemm_a4_fits(int64_t M, int64_t K, int wfmt, int64_t N, int64_t npad, int epilogue);
+int qvit_gemm_a4(const uint8_t* A, int64_t M, int64_t K, int64_t ldp, const void* Wp, int wfmt, int64_t N,
+                 int64_t npad, const float* d_act, const float* d_wt, const float* bias, int epilogue, void* C,
+                 int64_t ldc, int out_qtype, const float* out_d, const float* out_qm, const float* out_t,
+                 int out_levels, const void* epi_table, hipStream_t stream);
 
 /*
  * The backward GEMMs of QuantizeConv2d on the integer path are those of QuantizeLinear over the patch rows the

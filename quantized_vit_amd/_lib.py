@@ -197,6 +197,10 @@ _SIGNATURES = {
     "qvit_weight_code_sums": [_c_p, _i32, _i64, _i64, _c_p, _c_p],
     "qvit_gemm_a16_fits": [_i64, _i64, _i32, _i64, _i64],
     "qvit_gemm_a16": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _c_p, _c_p, _i64, _c_p],
+    "qvit_quantize_act_i4": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i64, _c_p],
+    "qvit_gemm_a4_fits": [_i64, _i64, _i32, _i64, _i64, _i32],
+    "qvit_gemm_a4": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i32, _c_p, _i64,
+                     _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
     "qvit_gemm_f32_nt": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i64, _c_p],
     "qvit_gemm_f32_tn": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _i64, _c_p, _i64, _c_p],
     "qvit_col2im_quant_backward": [_c_p, _i64, _c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
@@ -1044,6 +1048,49 @@ def gemm_a16(A: torch.Tensor, M: int, K: int, packed: torch.Tensor, wfmt: int, N
     _check(load().qvit_gemm_a16(_ptr(A), M, K, A.stride(1), _ptr(packed), wfmt, N, npad, _ptr(d_act), _ptr(d_wt),
                                 _ptr(bias_pad), _ptr(wsum), _ptr(Y), Y.stride(0), _stream(A.device)), "qvit_gemm_a16")
     return Y
+
+
+A4_MAX_LEVEL = 7   # QVIT_ACT_P4 holds codes in [-7, 7]
+
+
+def quantize_act_i4(x2d: torch.Tensor, qtype: int, d: Optional[torch.Tensor], qm: Optional[torch.Tensor],
+                    t: Optional[torch.Tensor], levels: int, out: torch.Tensor, kpad: int) -> torch.Tensor:
+    """quantize_act_i8 for layers of at most A4_MAX_LEVEL activation levels, written as packed nibbles (QVIT_ACT_P4):
+    out is uint8 [rows, >= kpad / 2], kpad a multiple of 128; the operand of gemm_a4."""
+    _require_gpu(x2d, "input")
+    assert x2d.dtype == torch.float32 and x2d.dim() == 2 and x2d.stride(1) == 1
+    rows, cols = x2d.shape
+    assert out.dtype == torch.uint8 and out.shape[0] == rows and out.stride(1) == 1
+    _check(load().qvit_quantize_act_i4(_ptr(x2d), rows, cols, x2d.stride(0), qtype, _ptr(d), _ptr(qm), _ptr(t),
+                                       levels, _ptr(out), out.stride(0), kpad, _stream(x2d.device)),
+           "qvit_quantize_act_i4")
+    return out
+
+
+def unpack_act_p4(packed: torch.Tensor, kpad: int) -> torch.Tensor:
+    """The int8 codes [rows, kpad] behind a QVIT_ACT_P4 buffer (code tracing and tests; plain torch ops)."""
+    g = packed[:, :kpad // 2].reshape(packed.shape[0], kpad // 128, 64).to(torch.int16)
+    nib = torch.stack((g & 15, g >> 4), dim=2)               # [rows, k-tile, low / high half, 64]
+    return (((nib + 8) & 15) - 8).to(torch.int8).reshape(packed.shape[0], kpad)
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_a4_fits(M: int, K: int, wfmt: int, N: int, npad: int, epilogue: int) -> bool:
+    """Whether qvit_gemm_a4 takes the shape (QVIT_W4R / QVIT_W8 images, K <= 65536, the five epilogues)."""
+    return bool(load().qvit_gemm_a4_fits(M, K, wfmt, N, npad, epilogue))
+
+
+def gemm_a4(A: torch.Tensor, M: int, K: int, packed: torch.Tensor, wfmt: int, N: int, npad: int,
+            d_act: Optional[torch.Tensor], d_wt: Optional[torch.Tensor], bias_pad: Optional[torch.Tensor],
+            epilogue: int, C: torch.Tensor, out_qtype: int = 0, out_d=None, out_qm=None, out_t=None,
+            out_levels: int = 0, epi_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qvit_gemm_a4: gemm's results byte for byte with the activation codes in QVIT_ACT_P4 (quantize_act_i4)."""
+    _require_gpu(A, "packed codes")
+    assert A.dtype == torch.uint8
+    _check(load().qvit_gemm_a4(_ptr(A), M, K, A.stride(0), _ptr(packed), wfmt, N, npad, _ptr(d_act), _ptr(d_wt),
+                               _ptr(bias_pad), epilogue, _ptr(C), C.stride(0), out_qtype, _ptr(out_d), _ptr(out_qm),
+                               _ptr(out_t), out_levels, _ptr(epi_table), _stream(A.device)), "qvit_gemm_a4")
+    return C
 
 
 def gemm_wgrad_splits(M: int, N: int, K: int) -> int:

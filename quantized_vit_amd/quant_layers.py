@@ -286,6 +286,13 @@ def _f32_gemm_ops() -> tuple:
 # the same on either route.
 A16_GEMM = os.environ.get("QVIT_A16_GEMM", "0") == "1"
 
+# QuantizeLinear's forward on the integer path with at most 7 activation levels (num_bits = 4 on both operands): with
+# QVIT_A4_GEMM=1 the activation codes are written as packed nibbles (qvit_quantize_act_i4, QVIT_ACT_P4: half the bytes
+# of the int8 codes) and contracted by qvit_gemm_a4 on the QVIT_W4R / QVIT_W8 images; the same bytes as
+# qvit_quantize_act_i8 + qvit_gemm. Off by default (measurement: DESIGN.md section 34). GEMM_SKINNY keeps precedence
+# at its row counts; the backward recomputes int8 codes on either route.
+A4_GEMM = os.environ.get("QVIT_A4_GEMM", "0") == "1"
+
 
 # The backward GEMMs of QuantizeConv2d (behind F.conv2d's backward), a switch of its own: "hip" runs both on the
 # project's kernels wherever the layer is eligible (groups 1, zero padding, packed codes), wgrad as qvit_gemm_wgrad
@@ -1170,14 +1177,37 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
                       plan.bias_pad, plan.extra["a16_wsum"], y)
         return y if ldy == plan.n else y[:, :plan.n]
 
+    def _a4_route(self, plan: QuantPlan, M: int) -> bool:
+        """The int path's forward runs on qvit_quantize_act_i4 + qvit_gemm_a4 (A4_GEMM)."""
+        if not (A4_GEMM and plan.int_path and abs(plan.level_act) <= _lib.A4_MAX_LEVEL):
+            return False
+        if GEMM_SKINNY and M <= GEMM_SKINNY_MAX_M:
+            return False
+        return _lib.gemm_a4_fits(M, plan.kpad, plan.gemm_weights()[1], plan.n, plan.npad, _lib.EPI_F32)
+
+    def _a4_rows(self, x2: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
+        """[M, k] fp32 rows -> the EPI_F32 contraction as [M, round_up(n, 4)] on packed 4-bit activation codes."""
+        M = x2.shape[0]
+        packed = torch.empty((M, plan.kpad // 2), dtype=torch.uint8, device=x2.device)
+        _lib.quantize_act_i4(x2, *plan.act_q, 0, packed, plan.kpad)
+        if CODE_TRACE is not None:
+            trace_codes(self, _lib.unpack_act_p4(packed, plan.kpad), plan.k)
+        out = torch.empty((M, _lib.round_up(plan.n, 4)), dtype=torch.float32, device=x2.device)
+        wimg, wfmt = plan.gemm_weights()
+        return _lib.gemm_a4(packed, M, plan.kpad, wimg, wfmt, plan.n, plan.npad, plan.d_act, plan.d_wt,
+                            plan.bias_pad, _lib.EPI_F32, out)
+
     def _forward_plan(self, input_: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
         if plan.int_path:
             x2 = input_.detach().reshape(-1, plan.k)
             if x2.dtype != torch.float32 or x2.stride(-1) != 1:
                 x2 = x2.float().contiguous()
-            codes = self._act_codes(x2, plan)
-            trace_codes(self, codes, plan.k)
-            out = self.gemm_codes(codes, plan, _lib.EPI_F32)
+            if self._a4_route(plan, x2.shape[0]):
+                out = self._a4_rows(x2, plan)
+            else:
+                codes = self._act_codes(x2, plan)
+                trace_codes(self, codes, plan.k)
+                out = self.gemm_codes(codes, plan, _lib.EPI_F32)
             if out.shape[1] != plan.n:
                 out = out[:, :plan.n].contiguous()
             return out.view(*input_.shape[:-1], plan.n)
