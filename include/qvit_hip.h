@@ -917,6 +917,56 @@ int qvit_gemm_a4(const uint8_t* A, int64_t M, int64_t K, int64_t ldp, const void
                  int out_levels, const void* epi_table, hipStream_t stream);
 
 /*
+ * W4A4 on the FP6 matrix instruction (QuantizeLinear.forward, quant_layers.py:495-499, with at most 7 levels on both
+ * operands). Every integer in [-7, 7] is an FP6 E2M3 value, so v_mfma_f32_16x16x128_f8f6f4 with both operands E2M3
+ * multiplies the codes themselves at twice the int8 rate; products are integers of magnitude <= 49 and with
+ * K <= 65536 every partial sum is below 2^24 in magnitude, so the fp32 accumulator holds qvit_gemm's int32 one.
+ *
+ * Element (OCP E2M3, 6 bits): bit 5 the sign; the magnitudes 0..7 are 0x00 0x08 0x10 0x14 0x18 0x1A 0x1C 0x1E; zero
+ * is always +0. A column group = 32 consecutive K-columns = 24 bytes, column j of the group at bits [6 j, 6 j + 6) of
+ * the 192 (dense, little-endian): a 16-byte head and an 8-byte tail. It is one lane's MFMA operand (6 registers).
+ *
+ * QVIT_ACT_F6: an [M][kpad] code matrix (kpad % 128 == 0, codes in [-7, 7]) as [M][ldp] bytes, ldp >= 3 kpad / 4,
+ * ldp % 16 == 0, 16-byte aligned. Per row and 128-column k-tile t 96 bytes at byte 96 t of the row: the heads of the
+ * column groups q = 0..3 (columns 128 t + 32 q .. + 31) at byte 16 q, their tails at byte 64 + 8 q: a 64-byte run and
+ * a 32-byte run, so the GEMM stages them with 16-byte DMA and a lane reads its operand with one aligned ds_read_b128
+ * and one aligned ds_read_b64, nothing between the read and the MFMA. Padding columns [K, kpad) hold 0; bytes
+ * [3 kpad / 4, ldp) are never touched.
+ *
+ * QVIT_W6F: the image of a QVIT_W4 plan (npad, kpad) in the same elements, 3 npad kpad / 4 bytes. Per (256-row tile
+ * tn, k-tile t) a chunk of 24576 bytes at chunk index tn (kpad / 128) + t; in it, per 16-row group g = 0..15 (packed
+ * rows 256 tn + 16 g .. + 15 in qvit_pack_weight's row order) 1536 bytes: the head of (row 16 g + (l & 15), column
+ * group l >> 4) at byte 16 l, its tail at byte 1024 + 8 l, l = 0..63 the GEMM lane: a wave's register loads are
+ * contiguous runs of 1 KiB and 512 bytes.
+ *
+ * qvit_quantize_act_f6: qvit_quantize_act_i4's arguments, check order (ldp >= 3 kpad / 4), quantizer and
+ * special-value rules; the output is QVIT_ACT_F6. Decoded, it is qvit_quantize_act_i8's codes whenever the saturation
+ * code is at most 7.
+ *
+ * qvit_pack_weight_f6: QVIT_W6F from a QVIT_W4 image. packed, out or bad_codes NULL: QVIT_ENULL; npad % QVIT_TILE_N,
+ * kpad % QVIT_TILE_K, kpad > 65536: QVIT_EINVAL; packed / out off 16 bytes: QVIT_EALIGN; out == packed: QVIT_EINVAL.
+ * The code -8 has no E2M3 value: it is written as 0 and counted into *bad_codes (device int32, which the caller has
+ * zeroed); an image with a non-zero count must not be used.
+ *
+ * qvit_gemm_f6: qvit_gemm's contraction and its five epilogues (QVIT_EPI_F32 .. QVIT_EPI_I32, same arithmetic, same
+ * code table) with A in QVIT_ACT_F6 and Wp in QVIT_W6F; C is qvit_gemm's on the same codes, byte for byte. Arguments
+ * and checks as qvit_gemm_a4 without wfmt (ldp >= 3 K / 4). M == 0 does nothing. qvit_gemm_f6_fits returns 1 exactly
+ * when the size checks (everything before ldp) and the epilogue's range pass.
+ * One workgroup per 256 weight rows x 128 rows; no atomics, no workspace: the same call gives the same bits.
+ * Special values: as qvit_gemm.
+ */
+int qvit_quantize_act_f6(const float* x, int64_t rows, int64_t cols, int64_t ldx, int qtype, const float* d_quant,
+                         const float* q_m, const float* t_quant, int levels, uint8_t* out, int64_t ldp,
+                         int64_t kpad, hipStream_t stream);
+int qvit_pack_weight_f6(const void* packed, int64_t npad, int64_t kpad, void* out, int32_t* bad_codes,
+                        hipStream_t stream);
+int qvit_gemm_f6_fits(int64_t M, int64_t K, int64_t N, int64_t npad, int epilogue);
+int qvit_gemm_f6(const uint8_t* A, int64_t M, int64_t K, int64_t ldp, const void* Wp, int64_t N, int64_t npad,
+                 const float* d_act, const float* d_wt, const float* bias, int epilogue, void* C, int64_t ldc,
+                 int out_qtype, const float* out_d, const float* out_qm, const float* out_t, int out_levels,
+                 const void* epi_table, hipStream_t stream);
+
+/*
  * The backward GEMMs of QuantizeConv2d on the integer path are those of QuantizeLinear over the patch rows the
  * forward contracted (qvit_im2col_quant_i8 + qvit_gemm): M = B OH OW rows of K = C kh kw columns.
  *   wgrad  qvit_gemm_wgrad on G2 (the [M][N] row view of the output gradient) and the im2col codes, which

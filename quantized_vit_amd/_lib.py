@@ -201,6 +201,11 @@ _SIGNATURES = {
     "qvit_gemm_a4_fits": [_i64, _i64, _i32, _i64, _i64, _i32],
     "qvit_gemm_a4": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _c_p, _c_p, _c_p, _i32, _c_p, _i64,
                      _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
+    "qvit_quantize_act_f6": [_c_p, _i64, _i64, _i64, _i32, _c_p, _c_p, _c_p, _i32, _c_p, _i64, _i64, _c_p],
+    "qvit_pack_weight_f6": [_c_p, _i64, _i64, _c_p, _c_p, _c_p],
+    "qvit_gemm_f6_fits": [_i64, _i64, _i64, _i64, _i32],
+    "qvit_gemm_f6": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _c_p, _i32, _c_p, _i64,
+                     _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
     "qvit_gemm_f32_nt": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i64, _c_p],
     "qvit_gemm_f32_tn": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _i64, _c_p, _i64, _c_p],
     "qvit_col2im_quant_backward": [_c_p, _i64, _c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
@@ -1090,6 +1095,72 @@ def gemm_a4(A: torch.Tensor, M: int, K: int, packed: torch.Tensor, wfmt: int, N:
     _check(load().qvit_gemm_a4(_ptr(A), M, K, A.stride(0), _ptr(packed), wfmt, N, npad, _ptr(d_act), _ptr(d_wt),
                                _ptr(bias_pad), epilogue, _ptr(C), C.stride(0), out_qtype, _ptr(out_d), _ptr(out_qm),
                                _ptr(out_t), out_levels, _ptr(epi_table), _stream(A.device)), "qvit_gemm_a4")
+    return C
+
+
+F6_MAX_LEVEL = 7   # FP6 E2M3 holds every integer in [-7, 7]
+_E2M3_MAG = (0x00, 0x08, 0x10, 0x14, 0x18, 0x1A, 0x1C, 0x1E)
+
+
+def quantize_act_f6(x2d: torch.Tensor, qtype: int, d: Optional[torch.Tensor], qm: Optional[torch.Tensor],
+                    t: Optional[torch.Tensor], levels: int, out: torch.Tensor, kpad: int) -> torch.Tensor:
+    """quantize_act_i8 for layers of at most F6_MAX_LEVEL activation levels, written as FP6 E2M3 fields (QVIT_ACT_F6):
+    out is uint8 [rows, >= 3 kpad / 4], kpad a multiple of 128; the operand of gemm_f6."""
+    _require_gpu(x2d, "input")
+    assert x2d.dtype == torch.float32 and x2d.dim() == 2 and x2d.stride(1) == 1
+    rows, cols = x2d.shape
+    assert out.dtype == torch.uint8 and out.shape[0] == rows and out.stride(1) == 1
+    _check(load().qvit_quantize_act_f6(_ptr(x2d), rows, cols, x2d.stride(0), qtype, _ptr(d), _ptr(qm), _ptr(t),
+                                       levels, _ptr(out), out.stride(0), kpad, _stream(x2d.device)),
+           "qvit_quantize_act_f6")
+    return out
+
+
+def unpack_act_f6(packed: torch.Tensor, kpad: int) -> torch.Tensor:
+    """The int8 codes [rows, kpad] behind a QVIT_ACT_F6 buffer (code tracing and tests; plain torch ops)."""
+    rows = packed.shape[0]
+    g = packed[:, :kpad // 4 * 3].reshape(rows, kpad // 128, 96).to(torch.int64)
+    # column group q of a k-tile: its 16-byte head at byte 16 q, its 8-byte tail at byte 64 + 8 q
+    by = torch.cat((g[:, :, :64].reshape(rows, -1, 4, 16), g[:, :, 64:].reshape(rows, -1, 4, 8)), dim=3)
+    w = (by.reshape(rows, -1, 4, 8, 3) << torch.tensor([0, 8, 16], device=packed.device)).sum(-1)   # 4 fields each
+    f = (w.unsqueeze(-1) >> torch.tensor([0, 6, 12, 18], device=packed.device)) & 63
+    mag = torch.full((32,), 99, dtype=torch.int64, device=packed.device)   # 99: not the field of an integer code
+    mag[torch.tensor(_E2M3_MAG, device=packed.device)] = torch.arange(8, device=packed.device)
+    k = mag[f & 31] * (1 - 2 * (f >> 5))
+    return k.to(torch.int8).reshape(rows, kpad)
+
+
+def pack_weight_f6(packed: torch.Tensor, npad: int, kpad: int) -> torch.Tensor:
+    """The FP6 image (QVIT_W6F) of a W4 image from pack_weight (qvit_pack_weight_f6): 3 npad kpad / 4 bytes, the
+    operand of gemm_f6. The code -8 has no E2M3 value: a plan that holds one raises QvitError (one synchronisation
+    per image)."""
+    _require_gpu(packed, "packed weights")
+    out = torch.empty(npad * kpad // 4 * 3, dtype=torch.uint8, device=packed.device)
+    bad = torch.zeros(1, dtype=torch.int32, device=packed.device)
+    _check(load().qvit_pack_weight_f6(_ptr(packed), npad, kpad, _ptr(out), _ptr(bad), _stream(packed.device)),
+           "qvit_pack_weight_f6")
+    if int(bad.item()):
+        raise QvitError(f"qvit_pack_weight_f6: {int(bad.item())} weight codes are -8, which FP6 E2M3 cannot hold")
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def gemm_f6_fits(M: int, K: int, N: int, npad: int, epilogue: int) -> bool:
+    """Whether qvit_gemm_f6 takes the shape (K <= 65536, the five epilogues)."""
+    return bool(load().qvit_gemm_f6_fits(M, K, N, npad, epilogue))
+
+
+def gemm_f6(A: torch.Tensor, M: int, K: int, image: torch.Tensor, N: int, npad: int,
+            d_act: Optional[torch.Tensor], d_wt: Optional[torch.Tensor], bias_pad: Optional[torch.Tensor],
+            epilogue: int, C: torch.Tensor, out_qtype: int = 0, out_d=None, out_qm=None, out_t=None,
+            out_levels: int = 0, epi_table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """qvit_gemm_f6: gemm's results byte for byte on the FP6 matrix instruction, A in QVIT_ACT_F6 (quantize_act_f6),
+    image from pack_weight_f6."""
+    _require_gpu(A, "FP6 codes")
+    assert A.dtype == torch.uint8
+    _check(load().qvit_gemm_f6(_ptr(A), M, K, A.stride(0), _ptr(image), N, npad, _ptr(d_act), _ptr(d_wt),
+                               _ptr(bias_pad), epilogue, _ptr(C), C.stride(0), out_qtype, _ptr(out_d), _ptr(out_qm),
+                               _ptr(out_t), out_levels, _ptr(epi_table), _stream(A.device)), "qvit_gemm_f6")
     return C
 
 

@@ -34,12 +34,11 @@
 #include <cstddef>
 #include <type_traits>
 
+#include "gemm_epi16.h"
 #include "qvit_common.h"
 #include "reduce_common.h"
 
 namespace {
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 constexpr int A4_BN = 256;              // weight rows per tile (one packed tile_n)
 constexpr int A4_BM = 128;              // activation rows per tile
@@ -93,126 +92,10 @@ QVIT_DEV void a4_barrier(v4i (&w)[8]) {
                : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7])::"memory");
 }
 
-struct A4Args {
-  const float* d_act;
-  const float* d_wt;
-  const float* bias;
-  int out_qtype;
-  const float* out_d;
-  const float* out_qm;
-  const float* out_t;
-  int out_levels;
-  const int8_t* table;   // optional code table of the int8 epilogues (qvit_epi_table_build)
-};
-
-// the int8 epilogues' quantizer state: the table's header, or the direct quantizer's scalars
-struct A4Quant {
-  bool use_table;
-  float c0, inv_w, top;
-  QParams qp;
-};
-
-// Row m, columns nb + 4 r + j of one 16-row group: gemm_skinny.hip's epilogue arithmetic (qvit_gemm's results).
-// SHIFT: the accumulators hold 2^SHIFT acc; alpha carries 2^-SHIFT.
-template <int EPI, int SHIFT>
-QVIT_DEV void a4_epilogue(const v4i (&acc)[4], int m, int nb, int N, void* __restrict__ C, int64_t ldc, float alpha,
-                          const A4Args& ep, const A4Quant& q) {
-  if constexpr (EPI == QVIT_EPI_I32) {
-    int32_t* dst = reinterpret_cast<int32_t*>(C) + (int64_t)m * ldc + nb;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const v4i a = v4i{acc[r][0] >> SHIFT, acc[r][1] >> SHIFT, acc[r][2] >> SHIFT, acc[r][3] >> SHIFT};   // exact
-      if (nb + 4 * r + 4 <= N) {
-        *reinterpret_cast<v4i*>(dst + 4 * r) = a;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (nb + 4 * r + j < N) dst[4 * r + j] = a[j];
-      }
-    }
-    return;
-  }
-  float v[16];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ep.bias != nullptr) b = *reinterpret_cast<const float4*>(ep.bias + nb + 4 * r);
-    v[4 * r + 0] = fmaf(alpha, (float)acc[r][0], b.x);
-    v[4 * r + 1] = fmaf(alpha, (float)acc[r][1], b.y);
-    v[4 * r + 2] = fmaf(alpha, (float)acc[r][2], b.z);
-    v[4 * r + 3] = fmaf(alpha, (float)acc[r][3], b.w);
-  }
-  if constexpr (EPI == QVIT_EPI_F32 || EPI == QVIT_EPI_F32_RESID) {
-    float* dst = reinterpret_cast<float*>(C) + (int64_t)m * ldc + nb;
-    float4 old[4];
-    if constexpr (EPI == QVIT_EPI_F32_RESID) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        if (nb + 4 * r + 4 <= N) old[r] = *reinterpret_cast<const float4*>(dst + 4 * r);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if (nb + 4 * r + 4 <= N) {
-        float4 o = make_float4(v[4 * r], v[4 * r + 1], v[4 * r + 2], v[4 * r + 3]);
-        if constexpr (EPI == QVIT_EPI_F32_RESID) {
-          o.x += old[r].x; o.y += old[r].y; o.z += old[r].z; o.w += old[r].w;
-        }
-        *reinterpret_cast<float4*>(dst + 4 * r) = o;
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (nb + 4 * r + j < N)
-            dst[4 * r + j] = (EPI == QVIT_EPI_F32_RESID) ? dst[4 * r + j] + v[4 * r + j] : v[4 * r + j];
-      }
-    }
-  } else {
-    // int8 codes: the table's entry {thr, lo | hi << 8} of v's bucket, or the quantizer itself; the same code for
-    // every v (the table is built from this very function)
-    uint32_t wd[4] = {0u, 0u, 0u, 0u};
-    if (q.use_table) {
-      const int8_t* ent = ep.table + sizeof(EpiTableHdr);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const uint2 e = *reinterpret_cast<const uint2*>(ent + 8 * epi_bucket(v[i], q.c0, q.inv_w, q.top));
-        const uint32_t code = (v[i] >= __uint_as_float(e.x)) ? ((e.y >> 8) & 0xffu) : (e.y & 0xffu);
-        wd[i >> 2] |= code << (8 * (i & 3));
-      }
-    } else {
-#pragma unroll 1
-      for (int i = 0; i < 16; ++i) {
-        const float x = (EPI == QVIT_EPI_I8_GELU) ? gelu_ref(v[i]) : v[i];
-        const uint32_t code = (uint32_t)(uint8_t)to_i8_sat(quant_code(x, q.qp));
-        // (a rolled loop: one copy of the quantizer; the word index is dynamic, so select it without indexing)
-        const uint32_t sh = code << (8 * (i & 3));
-        wd[0] |= (i >> 2) == 0 ? sh : 0u;
-        wd[1] |= (i >> 2) == 1 ? sh : 0u;
-        wd[2] |= (i >> 2) == 2 ? sh : 0u;
-        wd[3] |= (i >> 2) == 3 ? sh : 0u;
-      }
-    }
-    int8_t* dst = reinterpret_cast<int8_t*>(C) + (int64_t)m * ldc + nb;
-    const bool fast16 = ((ldc & 15) == 0) && ((((uintptr_t)C) & 15) == 0) && ((N & 15) == 0);
-    if (fast16) {
-      *reinterpret_cast<uint4*>(dst) = make_uint4(wd[0], wd[1], wd[2], wd[3]);
-    } else {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (nb + 4 * r + 4 <= N) {
-          *reinterpret_cast<uint32_t*>(dst + 4 * r) = wd[r];
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (nb + 4 * r + j < N) dst[4 * r + j] = (int8_t)((wd[r] >> (8 * j)) & 0xff);
-        }
-      }
-    }
-  }
-}
-
 template <int WFMT, int EPI>
 __global__ __launch_bounds__(256, 2) void gemm_a4_kernel(const uint8_t* __restrict__ A, int M, int K, int64_t ldp,
                                                          const int8_t* __restrict__ Wp, int N, int npad,
-                                                         void* __restrict__ C, int64_t ldc, A4Args ep) {
+                                                         void* __restrict__ C, int64_t ldc, Epi16Args ep) {
   constexpr bool W4 = WFMT == QVIT_W4R;
   constexpr bool I8OUT = (EPI == QVIT_EPI_I8 || EPI == QVIT_EPI_I8_GELU);
   constexpr int CHUNK = W4 ? 8192 : 16384;   // one (256-row tile, 64-deep stage) of the weight image
@@ -233,7 +116,7 @@ __global__ __launch_bounds__(256, 2) void gemm_a4_kernel(const uint8_t* __restri
   const int m0 = (t / nb_n) * A4_BM, tn = t % nb_n, n0 = tn * A4_BN;
   const int nkt = K / 128;
 
-  A4Quant q{false, 0.f, 0.f, 0.f, {}};
+  Epi16Quant q{false, 0.f, 0.f, 0.f, {}};
   if constexpr (I8OUT) {
     if (ep.table != nullptr) {
       const EpiTableHdr h = *reinterpret_cast<const EpiTableHdr*>(ep.table);
@@ -344,7 +227,7 @@ __global__ __launch_bounds__(256, 2) void gemm_a4_kernel(const uint8_t* __restri
 #pragma unroll
   for (int s = 0; s < A4_SM; ++s) {
     const int m = m0 + 16 * s + fr;
-    if (m < M) a4_epilogue<EPI, SHIFT>(acc[s], m, nb, N, C, ldc, alpha, ep, q);
+    if (m < M) epi16_row<EPI, SHIFT>(acc[s], m, nb, N, C, ldc, alpha, ep, q);
   }
 }
 
@@ -404,7 +287,7 @@ bool a4_sizes_ok(int64_t M, int64_t K, int wfmt, int64_t N, int64_t npad) {
 
 template <int WFMT, int EPI>
 int launch(const uint8_t* A, int64_t M, int64_t K, int64_t ldp, const void* Wp, int64_t N, int64_t npad, void* C,
-           int64_t ldc, const A4Args& ep, hipStream_t stream) {
+           int64_t ldc, const Epi16Args& ep, hipStream_t stream) {
   const unsigned grid = (unsigned)((a4_tiles(M, npad) + 7) / 8 * 8);
   hipLaunchKernelGGL((gemm_a4_kernel<WFMT, EPI>), dim3(grid), dim3(256), 0, stream, A, (int)M, (int)K, ldp,
                      reinterpret_cast<const int8_t*>(Wp), (int)N, (int)npad, C, ldc, ep);
@@ -413,7 +296,7 @@ int launch(const uint8_t* A, int64_t M, int64_t K, int64_t ldp, const void* Wp, 
 
 template <int WFMT>
 int dispatch_epi(int epilogue, const uint8_t* A, int64_t M, int64_t K, int64_t ldp, const void* Wp, int64_t N,
-                 int64_t npad, void* C, int64_t ldc, const A4Args& ep, hipStream_t stream) {
+                 int64_t npad, void* C, int64_t ldc, const Epi16Args& ep, hipStream_t stream) {
   switch (epilogue) {
     case QVIT_EPI_F32: return launch<WFMT, QVIT_EPI_F32>(A, M, K, ldp, Wp, N, npad, C, ldc, ep, stream);
     case QVIT_EPI_F32_RESID: return launch<WFMT, QVIT_EPI_F32_RESID>(A, M, K, ldp, Wp, N, npad, C, ldc, ep, stream);
@@ -464,7 +347,7 @@ extern "C" int qvit_gemm_a4(const uint8_t* A, int64_t M, int64_t K, int64_t ldp,
   if (epilogue != QVIT_EPI_I32 && (!d_act || !d_wt)) return QVIT_ENULL;
   if (qvit_misaligned(15, bias, epi_table)) return QVIT_EALIGN;
   if (M == 0) return QVIT_OK;
-  const A4Args ep{d_act, d_wt, bias, out_qtype, out_d, out_qm, out_t, out_levels,
+  const Epi16Args ep{d_act, d_wt, bias, out_qtype, out_d, out_qm, out_t, out_levels,
                   i8out ? reinterpret_cast<const int8_t*>(epi_table) : nullptr};
   if (wfmt == QVIT_W4R) return dispatch_epi<QVIT_W4R>(epilogue, A, M, K, ldp, Wp, N, npad, C, ldc, ep, stream);
   return dispatch_epi<QVIT_W8>(epilogue, A, M, K, ldp, Wp, N, npad, C, ldc, ep, stream);

@@ -293,6 +293,13 @@ A16_GEMM = os.environ.get("QVIT_A16_GEMM", "0") == "1"
 # at its row counts; the backward recomputes int8 codes on either route.
 A4_GEMM = os.environ.get("QVIT_A4_GEMM", "0") == "1"
 
+# The same layers with at most 7 levels on BOTH operands and 4-bit packed weights: with QVIT_F6_GEMM=1 the activation
+# codes are written as FP6 E2M3 fields (qvit_quantize_act_f6, QVIT_ACT_F6) and contracted with the QVIT_W6F image of
+# the weights on v_mfma_f32_16x16x128_f8f6f4 (qvit_gemm_f6): exact, the same bytes as qvit_quantize_act_i8 +
+# qvit_gemm. Off by default (measurement: DESIGN.md section 35). GEMM_SKINNY keeps precedence at its row counts,
+# F6_GEMM goes before A4_GEMM; the backward recomputes int8 codes on every route.
+F6_GEMM = os.environ.get("QVIT_F6_GEMM", "0") == "1"
+
 
 # The backward GEMMs of QuantizeConv2d (behind F.conv2d's backward), a switch of its own: "hip" runs both on the
 # project's kernels wherever the layer is eligible (groups 1, zero padding, packed codes), wgrad as qvit_gemm_wgrad
@@ -1177,6 +1184,29 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
                       plan.bias_pad, plan.extra["a16_wsum"], y)
         return y if ldy == plan.n else y[:, :plan.n]
 
+    def _f6_route(self, plan: QuantPlan, M: int) -> bool:
+        """The int path's forward runs on qvit_quantize_act_f6 + qvit_gemm_f6 (F6_GEMM)."""
+        if not (F6_GEMM and plan.int_path and plan.wfmt == _lib.W4 and abs(plan.level_wt) <= _lib.F6_MAX_LEVEL
+                and abs(plan.level_act) <= _lib.F6_MAX_LEVEL):
+            return False
+        if GEMM_SKINNY and M <= GEMM_SKINNY_MAX_M:
+            return False
+        return _lib.gemm_f6_fits(M, plan.kpad, plan.n, plan.npad, _lib.EPI_F32)
+
+    def _f6_rows(self, x2: torch.Tensor, plan: QuantPlan) -> torch.Tensor:
+        """[M, k] fp32 rows -> the EPI_F32 contraction as [M, round_up(n, 4)] on FP6 codes of both operands. The
+        QVIT_W6F image is made from the plan's packed codes on first use and lives with the plan."""
+        M = x2.shape[0]
+        if "w6f" not in plan.extra:
+            plan.extra["w6f"] = _lib.pack_weight_f6(plan.packed_codes(), plan.npad, plan.kpad)
+        codes = torch.empty((M, plan.kpad // 4 * 3), dtype=torch.uint8, device=x2.device)
+        _lib.quantize_act_f6(x2, *plan.act_q, 0, codes, plan.kpad)
+        if CODE_TRACE is not None:
+            trace_codes(self, _lib.unpack_act_f6(codes, plan.kpad), plan.k)
+        out = torch.empty((M, _lib.round_up(plan.n, 4)), dtype=torch.float32, device=x2.device)
+        return _lib.gemm_f6(codes, M, plan.kpad, plan.extra["w6f"], plan.n, plan.npad, plan.d_act, plan.d_wt,
+                            plan.bias_pad, _lib.EPI_F32, out)
+
     def _a4_route(self, plan: QuantPlan, M: int) -> bool:
         """The int path's forward runs on qvit_quantize_act_i4 + qvit_gemm_a4 (A4_GEMM)."""
         if not (A4_GEMM and plan.int_path and abs(plan.level_act) <= _lib.A4_MAX_LEVEL):
@@ -1202,7 +1232,9 @@ class QuantizeLinear(nn.Linear, QuantizeMixin):
             x2 = input_.detach().reshape(-1, plan.k)
             if x2.dtype != torch.float32 or x2.stride(-1) != 1:
                 x2 = x2.float().contiguous()
-            if self._a4_route(plan, x2.shape[0]):
+            if self._f6_route(plan, x2.shape[0]):
+                out = self._f6_rows(x2, plan)
+            elif self._a4_route(plan, x2.shape[0]):
                 out = self._a4_rows(x2, plan)
             else:
                 codes = self._act_codes(x2, plan)
