@@ -62,6 +62,10 @@
  *                             quant_layers.py:495-499 and its backward where neither operand is a code image
  *                             (train.py:247-250 builds the model at num_bits = 32): fp32 x fp32 on bf16 MFMA, both
  *                             operands split into three exact bf16 terms, six products per element pair.
+ *   qvit_pack_weight_b3 / qvit_gemm_f32w
+ *                             nn.Linear of the frozen full-precision teacher (train.py:290-316, utils.py:268-274): the
+ *                             same arithmetic with the weights split once into an image in the GEMM's LDS order
+ *                             (QVIT_WB3), optionally three products instead of six, GELU or residual add fused.
  *   qvit_quantize_act_i16 / qvit_gemm_a16 / qvit_weight_code_sums
  *                             quant_layers.py:495-499 with 9- to 16-bit activation codes: the codes as two int8 digit
  *                             planes, contracted with the weight digits on int8 MFMA, exact.
@@ -145,6 +149,7 @@ extern "C" {
 #define QVIT_EPI_I32        4  /* C[m,n]  = acc                                      (int32, exact)  */
 #define QVIT_EPI_QKV_SPLIT  5  /* fp16 hi/lo planes of in_scale (d_act d_wt acc + bias[n]); only via
                                   qvit_gemm_qkv_split (qvit_gemm rejects it)                        */
+#define QVIT_EPI_F32_GELU   6  /* C[m,n]  = gelu(acc + bias[n])                      (fp32); qvit_gemm_f32w only */
 
 /* ---- qvit_ultra_conv epilogues (UltraNet, 4-bit quantization/mymodel.py) -------------------- */
 #define QVIT_ULTRA_CODES       0  /* codes = rne(clamp(bn(acc/den), 0, 1) (2^a_bit-1))       (uint codes) */
@@ -830,6 +835,44 @@ int qvit_gemm_f32_nt(const float* A, int64_t M, int64_t K, int64_t lda, const fl
 int64_t qvit_gemm_f32_tn_workspace_bytes(int64_t M, int64_t I, int64_t J);
 int qvit_gemm_f32_tn(const float* A, int64_t M, int64_t I, int64_t lda, const float* B, int64_t J, int64_t ldb,
                      float* C, int64_t ldc, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
+/*
+ * nn.Linear of a model that is built once and never trained: the full-precision distillation teacher of the
+ * reference's driver (train.py:290-316 builds it, leaves it unquantized and freezes it; utils.py:268-274 runs it once
+ * per step under no_grad). qvit_gemm_f32_nt's arithmetic with the weight operand split once, ahead of time.
+ *
+ * QVIT_WB3: fp32 weights [N][K] as the bf16 terms b1, b2, b3 of the exact split b = b1 + b2 + b3 (truncation, as
+ * qvit_gemm_f32_nt), in the GEMM's stage order. nst = ceil(K / 32), ntile = ceil(N / 128). Per (weight tile tn, stage
+ * st) `planes` planes of [128 rows][32 k] bf16, 8192 bytes each, term p of stage (tn, st) at byte
+ * ((tn nst + st) planes + p) 8192; in a plane, element k (0 .. 31) of row r (0 .. 127) at byte
+ * 64 r + 16 ((k / 8) ^ ((r / 4) & 3)) + 2 (k % 8). Rows past N and columns past K hold zero.
+ *   planes : 3 (all terms) or 2 (b1, b2 only), else QVIT_EINVAL.
+ * qvit_pack_weight_b3_bytes returns ntile nst planes 8192, or QVIT_EINVAL (N outside [1, 2^24], K outside [1, 2^30],
+ * planes).
+ * qvit_pack_weight_b3 writes every byte of the image.
+ *   W      : fp32 [N][ldw], ldw >= K and ldw % 4 == 0, 16-byte aligned; rows are read in whole 16-byte groups (the last
+ *            group of a row may reach up to 3 floats into the row's padding, which never reaches the image).
+ *   image  : image_bytes >= the query's value (else QVIT_EINVAL), 16-byte aligned.
+ *
+ * qvit_gemm_f32w  C[m][n] = epi(sum_k A[m][k] W[n][k] + bias[n]).
+ *   A, lda, bias, C, ldc : as qvit_gemm_f32_nt (M in [0, 2^24], M == 0 does nothing).
+ *   Wimg, planes, image_bytes : a QVIT_WB3 image of the [N][K] weights, its plane count and size.
+ *   terms  : 6 (planes == 3): the six products and the order of qvit_gemm_f32_nt, its bound (4 K + 9) 2^-24 (|A||W|).
+ *            3 (planes == 2): a2b1, a1b2, a1b1 only (A split into two terms); the dropped products add at most
+ *            (2^-13 + 2^-20) (|A||W|) to that bound. Any other value or pairing is QVIT_EINVAL.
+ *   epilogue : QVIT_EPI_F32 (store v = acc + bias[n]), QVIT_EPI_F32_GELU (store gelu(v), the function of qvit_gelu_f32),
+ *            QVIT_EPI_F32_RESID (C[m][n] = C[m][n] + v, one fp32 add); else QVIT_EINVAL.
+ * Checks in this order: NULL A / Wimg / C (QVIT_ENULL); planes, terms, epilogue, sizes, strides below the extent,
+ * image_bytes (QVIT_EINVAL); lda or ldc % 4, bases not 16-byte aligned, bias not 4-byte aligned (QVIT_EALIGN).
+ * No split of K and no atomics: the same call gives the same bits. A NaN or Inf in A[m][k] makes row m of C NaN and
+ * changes no other bit. Columns [N, ldc) of C are not written.
+ */
+int64_t qvit_pack_weight_b3_bytes(int64_t N, int64_t K, int planes);
+int qvit_pack_weight_b3(const float* W, int64_t N, int64_t K, int64_t ldw, int planes, void* image,
+                        int64_t image_bytes, hipStream_t stream);
+int qvit_gemm_f32w(const float* A, int64_t M, int64_t K, int64_t lda, const void* Wimg, int planes,
+                   int64_t image_bytes, int64_t N, int terms, const float* bias, int epilogue, float* C, int64_t ldc,
+                   hipStream_t stream);
 
 /*
  * QuantizeLinear.forward (quant_layers.py:495-499) in WEIGHT_AND_ACTIVATION mode with activation levels 128 .. 32767

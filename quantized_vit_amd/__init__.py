@@ -31,6 +31,7 @@ from .qat_optim import QuantAwareOptimizer
 from .qat_prune import PruneGroup, vit_head_prune_groups, vit_mlp_prune_groups
 from .compress import compress_pruned_heads, compress_pruned_mlp
 from .losses import TrainLoss, TrainLossResult, mixup
+from .teacher import FrozenLinear, prepare_teacher
 
 __all__ = [
     "LAYER_TO_QUANTLAYER", "NanInGradientError", "QuantizationMode", "QuantizationType", "QuantizeConv2d",
@@ -39,4 +40,5 @@ __all__ = [
     "collect_input_absmax", "quantize_pretrained", "search_activation_quant", "search_weight_quant",
     "set_activation_quant", "QuantAwareOptimizer", "PruneGroup", "vit_mlp_prune_groups", "compress_pruned_mlp",
     "vit_head_prune_groups", "compress_pruned_heads", "TrainLoss", "TrainLossResult", "mixup",
+    "FrozenLinear", "prepare_teacher",
 ]

@@ -38,6 +38,7 @@ EPI_I8_GELU = 2
 EPI_I8 = 3
 EPI_I32 = 4
 EPI_QKV_SPLIT = 5   # qvit_gemm_qkv_split only
+EPI_F32_GELU = 6    # qvit_gemm_f32w only
 
 ATT_F32 = 0
 ATT_I8 = 1
@@ -208,6 +209,8 @@ _SIGNATURES = {
                      _i32, _c_p, _c_p, _c_p, _i32, _c_p, _c_p],
     "qvit_gemm_f32_nt": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _c_p, _i64, _c_p],
     "qvit_gemm_f32_tn": [_c_p, _i64, _i64, _i64, _c_p, _i64, _i64, _c_p, _i64, _c_p, _i64, _c_p],
+    "qvit_pack_weight_b3": [_c_p, _i64, _i64, _i64, _i32, _c_p, _i64, _c_p],
+    "qvit_gemm_f32w": [_c_p, _i64, _i64, _i64, _c_p, _i32, _i64, _i64, _i32, _c_p, _i32, _c_p, _i64, _c_p],
     "qvit_col2im_quant_backward": [_c_p, _i64, _c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                    _i32, _i32, _c_p, _c_p, _c_p, _f32, _f32, _c_p, _c_p, _c_p, _i64, _c_p],
     "qvit_conv_wonly": [_c_p, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _c_p, _i32,
@@ -264,6 +267,7 @@ INT64_FUNCS = {
     "qvit_attention_backward_workspace_bytes": [_i64, _i64, _i64],
     "qvit_gemm_wgrad_workspace_bytes": [_i64, _i64, _i64],
     "qvit_gemm_f32_tn_workspace_bytes": [_i64, _i64, _i64],
+    "qvit_pack_weight_b3_bytes": [_i64, _i64, _i32],
     "qvit_col2im_quant_backward_workspace_bytes": [_i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
                                                    _i32],
     "qvit_ultra_weight_quant_backward_workspace_bytes": [_i64],
@@ -1288,6 +1292,48 @@ def gemm_f32_tn(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = 
                                 _ptr(workspace), workspace.numel() * workspace.element_size(), _stream(a.device)),
            "qvit_gemm_f32_tn")
     return out
+
+
+def pack_weight_b3(w: torch.Tensor, planes: int = 3) -> torch.Tensor:
+    """The QVIT_WB3 image of fp32 weights w [N, K] (qvit_pack_weight_b3): their bf16 terms b1, b2 (, b3 with
+    planes = 3) in qvit_gemm_f32w's stage order, a uint8 tensor. Built once per frozen weight."""
+    w = _f32_gemm_operand(w.detach(), "w")
+    N, K = w.shape
+    nbytes = int(load().qvit_pack_weight_b3_bytes(N, K, planes))
+    if nbytes < 0:
+        _check(nbytes, "qvit_pack_weight_b3_bytes")
+    image = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    _check(load().qvit_pack_weight_b3(_ptr(w), N, K, w.stride(0), planes, _ptr(image), nbytes, _stream(w.device)),
+           "qvit_pack_weight_b3")
+    return image
+
+
+def gemm_f32w(a: torch.Tensor, image: torch.Tensor, n: int, terms: int = 6, bias: Optional[torch.Tensor] = None,
+              epilogue: int = EPI_F32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """epi(a @ W^T + bias) on qvit_gemm_f32w: a [M, K] fp32 on the device (copied into padded rows when off the
+    kernel's alignment), `image` the pack_weight_b3 image of W [n, K] with 3 planes for terms = 6 and 2 for terms = 3.
+    epilogue EPI_F32 / EPI_F32_GELU write `out` (or a new [M, n] tensor); EPI_F32_RESID adds into `out`, which must
+    then be given in the kernel's alignment (fp32, unit column stride, row stride % 4 == 0, 16-byte base)."""
+    a = _f32_gemm_operand(a, "a")
+    M, K = a.shape
+    if bias is not None:
+        _require_gpu(bias, "bias")
+        bias = bias.detach().float().contiguous()
+        assert bias.shape == (n,)
+    y = out
+    if y is None or y.dtype != torch.float32 or y.stride(1) != 1 or y.stride(0) % 4 or y.data_ptr() % 16:
+        if epilogue == EPI_F32_RESID:
+            raise QvitError("gemm_f32w: EPI_F32_RESID updates `out` in place and needs it in the kernel's alignment")
+        y = torch.empty((M, round_up(n, 4)), dtype=torch.float32, device=a.device)[:, :n]
+    assert y.shape == (M, n) and y.is_cuda and image.is_cuda and image.dtype == torch.uint8
+    if M > 0:   # (an empty tensor has no device pointer to hand over)
+        _check(load().qvit_gemm_f32w(_ptr(a), M, K, a.stride(0), _ptr(image), 3 if terms == 6 else 2, image.numel(),
+                                     n, terms, _ptr(bias), epilogue, _ptr(y), y.stride(0), _stream(a.device)),
+               "qvit_gemm_f32w")
+    if out is not None and y is not out:
+        out.copy_(y)
+        return out
+    return y
 
 
 def conv_out_hw(H: int, W: int, kernel_size, stride, padding, dilation) -> Tuple[int, int]:

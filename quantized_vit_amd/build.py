@@ -23,12 +23,13 @@ SOURCES = ["quant_kernels.hip", "quant_backward.hip", "train_fuse.hip", "gemm_w4
            "gemm_wonly.hip", "gemm_wgrad.hip", "attention.hip", "attention_backward.hip", "qkv_attention.hip",
            "ultra_conv.hip", "ultra_backward.hip", "ultra_bn_fuse.hip", "conv_backward.hip", "u8_input.hip",
            "quant_error.hip", "qat_step.hip", "prune_step.hip", "train_loss.hip", "group_lasso.hip",
-           "gemm_skinny.hip", "gemm_f32.hip", "gemm_a16.hip", "gemm_a4.hip", "gemm_f6.hip"]
+           "gemm_skinny.hip", "gemm_f32.hip", "gemm_a16.hip", "gemm_a4.hip", "gemm_f6.hip", "gemm_f32w.hip"]
 # sources with inline-asm register loads: their device assembly is kept beside the objects (the very code in the
 # library) for tools/asm_load_check.py (tests/test_asm_loads.py)
 ASM_CHECKED = ["gemm_w4a8.hip", "ultra_conv.hip"]
 HEADERS = ["qvit_common.h", "attn_common.h", "attn32.h", "ln_common.h", "reduce_common.h", "quant_bwd_common.h",
-           "bf16x3.h", "ultra_quant_common.h", "diag_stamps.h", "qat_common.h", "prune_common.h", "gemm_epi16.h"]
+           "bf16x3.h", "ultra_quant_common.h", "diag_stamps.h", "qat_common.h", "prune_common.h", "gemm_epi16.h",
+           "gemm_f32_common.h"]
 
 HIPCC_FLAGS = [
     f"--offload-arch={ARCH}",
@@ -44,13 +45,13 @@ HIPCC_FLAGS = [
 # flags of single sources, after the common ones. train_loss.hip: scalar fp32 arithmetic only (no packed
 # v_pk_*_f32 forms from the vectoriser: the kernel is bound by its loads, and the scalar forms round as written);
 # group_lasso.hip likewise; gemm_skinny.hip: its fp32 epilogue is one fma per element, kept in the scalar form;
-# gemm_f32.hip: the bf16 split's subtractions and the bias add, likewise; gemm_a16.hip: the quantizer's clamps;
+# gemm_f32.hip and gemm_f32w.hip: the bf16 split's subtractions and the bias add, likewise; gemm_a16.hip: the quantizer's clamps;
 # gemm_a4.hip and gemm_f6.hip: the quantizer's clamps and the fp32 epilogue's fma
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 SOURCE_FLAGS = {"train_loss.hip": _NO_PACKED_FP32, "group_lasso.hip": _NO_PACKED_FP32,
                 "gemm_skinny.hip": _NO_PACKED_FP32, "gemm_f32.hip": _NO_PACKED_FP32,
                 "gemm_a16.hip": _NO_PACKED_FP32, "gemm_a4.hip": _NO_PACKED_FP32,
-                "gemm_f6.hip": _NO_PACKED_FP32}
+                "gemm_f6.hip": _NO_PACKED_FP32, "gemm_f32w.hip": _NO_PACKED_FP32}
 
 
 def source_flags(src: str) -> list:

@@ -30,7 +30,7 @@
 //   is written by the first launch: the workspace's contents do not matter.
 // Tiles are dealt to the eight XCDs in contiguous ranges (n tiles fastest: the tiles that share an A panel share an
 // L2). Index arithmetic: rows and columns in int32 (extents <= 2^24, K and M <= 2^30), element offsets in int64.
-#include "bf16x3.h"
+#include "gemm_f32_common.h"
 #include "reduce_common.h"
 
 namespace {
@@ -38,38 +38,11 @@ namespace {
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef short s8v __attribute__((ext_vector_type(8)));
 
-constexpr int FG_BT = 128;               // tile side (both output axes)
-constexpr int FG_BK = 32;                // contraction per stage: one MFMA
-constexpr int FG_PLANE = FG_BT * FG_BK * 2;   // one bf16 plane: 8 KiB
 constexpr int FG_STAGE = 6 * FG_PLANE;   // a1 a2 a3 b1 b2 b3
 constexpr int FG_MAX_SPLITS = 16;
 constexpr int FG_TARGET_WGS = 512;
 
-// The six products of the four MFMA tiles of one accumulator row, smallest first: a3b1, a1b3, a2b2, a2b1, a1b2, a1b1
-// (each accumulator sees them in that order; the four tiles of a round are independent). r: the planes b1 b2 b3 of
-// the operand that supplies the MFMAs' rows, per tile; c: the planes a1 a2 a3 of the one that supplies their columns.
-QVIT_DEV void mma6(f4 (&acc)[4], const bf8 (&r)[4][3], const bf8 (&c)[3]) {
-#define FG_ROUND(pa, pb)                                                                      \
-  _Pragma("unroll") for (int t = 0; t < 4; ++t) acc[t] =                                      \
-      __builtin_amdgcn_mfma_f32_16x16x32_bf16(r[t][pb], c[pa], acc[t], 0, 0, 0);
-  FG_ROUND(2, 0) FG_ROUND(0, 2) FG_ROUND(1, 1) FG_ROUND(1, 0) FG_ROUND(0, 1) FG_ROUND(0, 0)
-#undef FG_ROUND
-}
-
-// this workgroup's unit under the XCD deal: XCD x (blocks x, x + 8, ...) walks a contiguous range of units
-QVIT_DEV int xcd_unit(int total) {
-  const int per = (total + 7) >> 3;
-  return (int)(blockIdx.x & 7) * per + (int)(blockIdx.x >> 3);
-}
-
-QVIT_DEV void split4(f4 v, uint2& p1, uint2& p2, uint2& p3) {
-  split_bf16x3(v[0], v[1], p1.x, p2.x, p3.x);
-  split_bf16x3(v[2], v[3], p1.y, p2.y, p3.y);
-}
-
-// ---- NT ------------------------------------------------------------------------------------------------------
-QVIT_DEV int nt_off(int r, int ch) { return 64 * r + 16 * (ch ^ ((r >> 2) & 3)); }
-
+// ---- NT (nt_off: gemm_f32_common.h) ----------------------------------------------------------------------------
 __global__ __launch_bounds__(256, 2) void gemm_f32_nt_kernel(const float* __restrict__ A, int M, int K, int64_t lda,
                                                              const float* __restrict__ B, int N, int64_t ldb,
                                                              const float* __restrict__ bias, float* __restrict__ C,
@@ -294,9 +267,6 @@ __global__ __launch_bounds__(256, 2) void gemm_f32_tn_kernel(const float* __rest
 #pragma unroll
     for (int jt = 0; jt < 4; ++jt) *reinterpret_cast<f4*>(pb + (int64_t)16 * it * jpad + 16 * jt) = acc[it][jt];
 }
-
-int64_t round128(int64_t v) { return (v + 127) / 128 * 128; }
-int64_t tiles128(int64_t r, int64_t c) { return (round128(r) / FG_BT) * (round128(c) / FG_BT); }
 
 // rows x cols: the output; depth: the contraction. (Grids and split * tile counts fit int32.)
 bool f32_sizes_ok(int64_t depth, int64_t rows, int64_t cols, int64_t min_rows) {

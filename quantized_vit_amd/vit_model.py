@@ -36,6 +36,7 @@ from . import _lib
 from . import quant_layers as _ql
 from .quant_layers import (QuantizationMode, QuantizeConv2d, QuantizeLinear, _autograd_live, epilogue_table,
                            trace_codes)
+from .teacher import FrozenLinear
 
 # The residual GEMMs (proj, fc2) run the following LayerNorm + quantizer behind their tiles (qvit_gemm_resid_ln)
 # instead of as a separate launch when QVIT_FUSE_LN=1 (or FUSE_RESID_LN = True). Off by default: the fused
@@ -363,6 +364,30 @@ class Block(nn.Module):
         """In-place fused block on a contiguous [B, N, C] fp32 residual buffer (owned by caller)."""
         return self.forward_fused_chain_(x)[0]
 
+    def frozen_ok(self, x: torch.Tensor) -> bool:
+        """The full-precision teacher's route (teacher.prepare_teacher): all four linears FrozenLinear on their
+        kernel, nothing for autograd to record, nothing between the GEMMs that their epilogues do not compute."""
+        a, m = self.attn, self.mlp
+        return (x.dim() == 3 and x.shape[0] * x.shape[1] > 0 and x.shape[2] % 4 == 0
+                and all(isinstance(l, FrozenLinear) and l.hip_ok(x) for l in (a.qkv, a.proj, m.fc1, m.fc2))
+                and not _autograd_live(self, x)
+                and isinstance(m.act, nn.GELU) and m.act.approximate == "none"
+                and _inactive(self.drop_path) and _inactive(a.attn_drop) and _inactive(a.proj_drop)
+                and _inactive(m.drop))
+
+    def forward_frozen_(self, x: torch.Tensor) -> torch.Tensor:
+        """In place on a contiguous [B, N, C] fp32 residual buffer (owned by caller): proj and fc2 add into it
+        (EPI_F32_RESID, torch's x + y rounding), fc1 applies the exact GELU (EPI_F32_GELU)."""
+        a, m = self.attn, self.mlp
+        B, N, C = x.shape
+        x2 = x.view(B * N, C)
+        qkv = a.qkv.gemm(self.norm1(x).view(B * N, C))
+        y = a.core(qkv.reshape(B, N, -1), B, N)
+        a.proj.gemm(y.reshape(B * N, C), _lib.EPI_F32_RESID, x2)
+        h = m.fc1.gemm(self.norm2(x).view(B * N, C), _lib.EPI_F32_GELU)
+        m.fc2.gemm(h, _lib.EPI_F32_RESID, x2)
+        return x
+
     def ln_fusable(self, x2: torch.Tensor, norm: nn.LayerNorm, p_res: QuantPlan) -> bool:
         """Whether the residual GEMM with plan p_res can run `norm` (+ the next quantizer) behind its tiles."""
         C = x2.shape[1]
@@ -534,6 +559,8 @@ class Block(nn.Module):
     def forward(self, x):
         if self.fused_ok(x):
             return self.forward_fused_(x.contiguous().clone())
+        if self.frozen_ok(x):
+            return self.forward_frozen_(x.contiguous().clone())
         if TRAIN_FUSE and x.dim() == 3 and _autograd_live(self, x):
             return self.forward_train_fused(x)
         x = x + self.drop_path(self.attn(self.norm1(x)))
@@ -633,6 +660,9 @@ class VisionTransformer(nn.Module):
                         and not torch.is_grad_enabled() and x.shape[1] >= self.num_tokens)
                 x, codes = blk.forward_fused_chain_(x.contiguous(), codes, nb, last=last,
                                                     num_tokens=self.num_tokens)
+            elif isinstance(blk, Block) and blk.frozen_ok(x):   # the frozen teacher: the same buffer, in place
+                codes = None
+                x = blk.forward_frozen_(x.contiguous())
             else:
                 codes = None
                 x = blk(x)
